@@ -15,7 +15,14 @@ weights, factor 4, weight-norm), fp32, per-GPU batch 32 (weak scaling: global ba
 Prints ONE JSON line (rank 0).  `value` = whole-node training steps/s = N * K / T, where every rank
 runs K steps of per-GPU batch 32 and T is the max over ranks of the barrier-bracketed wall time.
 
-How the per-kernel numbers are taken (no hand-tuned corrections):
+A plain run sets up, warms up, times the K steps and prints the line (headline fields only).  `--full` adds
+everything else the line used to carry: the instrumented pass, forward-only latencies, per-kernel replays and
+rooflines, the arithmetic / bf16-storage variants, the secondary workloads and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step left its caller (the loss and the trainer's flat
+parameter / AdamW-moment buffers) as DIR/<name>.npy; inputs and initial weights are seeded, so two builds
+can be compared output for output.
+
+How the per-kernel numbers of `--full` are taken (no hand-tuned corrections):
   * `avg_us` of a hot kernel = one pair of HIP events around 200 back-to-back replays of a launch captured from the middle
     layer of a real training step (same arguments, same stream), divided by 200;
   * `in_step_event_us` = mean of raw HIP-event brackets around sampled launches inside real training steps -- an instrumented
@@ -53,6 +60,7 @@ BF16X3_PEAK_TFLOPS = 2500.0 / 6.0
 FP16X2_PEAK_TFLOPS = 2500.0 / 3.0
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E spec peak
 REPLAYS = 200
+DUMP_MAX_FLOATS = 4 << 20       # per dumped array (16 MiB): larger buffers are written as a fixed, seeded sample
 
 HOT = ["spectral_fused", "spectral_fused(adj)", "spectral_staged_pair", "spectral_staged_pair(adj)", "ff_fwd", "ff_bwd_data",
        "ff_bwd_weights_partial", "fw_grad_partial"]
@@ -389,6 +397,89 @@ def secondary_workloads(dev, steps=10, warmup=3):
     return out
 
 
+def dump_outputs(path, loss, trainer):
+    """What the timed path hands its caller after its last step: the loss train_step returned and the state it advanced (the
+    flat parameter buffer and the AdamW moments), as float32 <name>.npy.  A buffer above DUMP_MAX_FLOATS is written as the
+    values at a fixed set of indices (seeded by its length, sorted), so that two builds write the same sample."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("loss", loss), ("params", trainer.pflat), ("adam_m", trainer.m), ("adam_v", trainer.v)):
+        a = t.detach().float().reshape(-1).cpu().numpy()
+        if a.size > DUMP_MAX_FLOATS:
+            a = a[np.sort(np.random.default_rng(a.size).choice(a.size, DUMP_MAX_FLOATS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs of the last timed step written to {path}")
+
+
+def distributed_info(args, world, rccl_world, steps_per_s, per_rank, allreduce_us):
+    """The `distributed` block of an N > 1 line (None at N = 1); refuses an `nccl` run that torch reports no RCCL version for."""
+    if world == 1:
+        return None
+    try:
+        ver = ".".join(str(v) for v in torch.cuda.nccl.version())
+    except Exception:  # noqa: BLE001
+        ver = None
+    dist_info = dict(world_size=torch.distributed.get_world_size(), world_size_counted_by_all_reduce=rccl_world,
+                     backend=torch.distributed.get_backend(), rccl_version=ver, hip=torch.version.hip,
+                     per_rank=per_rank, allreduce_us=allreduce_us,
+                     efficiency_vs_n1=(round(steps_per_s / (world * args.n1_steps_per_s), 4) if args.n1_steps_per_s > 0 else None),
+                     n1_steps_per_s=(args.n1_steps_per_s or None),
+                     launch="one process per GPU (torch.distributed.run; `python bench.py --gpus N` spawns them itself)")
+    if dist_info["backend"] == "nccl" and not ver:
+        raise SystemExit("backend nccl (= RCCL on ROCm) but torch reports no RCCL version: not an RCCL run, no line printed")
+    return dist_info
+
+
+def rates(args, world, elapsed):
+    """(optimiser steps/s, `value`) of a timed region of args.steps steps that took `elapsed` s (max over ranks)."""
+    opt_steps_per_s = args.steps / elapsed                    # optimiser steps of the GLOBAL batch (B x world samples each)
+    # weak scaling: per-GPU-batch steps summed over ranks (= N x optimiser steps/s: what the driver divides by N x the
+    # one-GPU value); strong scaling (--global-batch): the global batch is fixed, so optimiser steps/s is the figure
+    return opt_steps_per_s, (opt_steps_per_s if args.global_batch else world * args.steps / elapsed)
+
+
+def result_line(args, world, trainer, B, G, K, elapsed, per_step_ms, loss_val):
+    """The headline fields of the JSON line: everything here comes from the timed region."""
+    strong = bool(args.global_batch)
+    opt_steps_per_s, steps_per_s = rates(args, world, elapsed)
+    return {
+        "metric": ("training-steps/sec (whole node), FNOPlus2DBlock %dL %dx%d modes %d" % (args.layers, G, G, K) if args.plus else
+                   "training-steps/sec (whole node), F-FNO 24L 64x64 torus (torus_li/markov/24_layers)"
+                   if (G, args.layers, K) == (64, 24, 16) else
+                   "training-steps/sec (whole node), F-FNO %dL %dx%d modes %d" % (args.layers, G, G, K)),
+        "value": round(steps_per_s, 3),
+        "unit": ("optimiser steps/s at global batch %d" % (B * world)) if strong else
+                ("steps/s (per-GPU batch %d, summed over ranks)" % B),
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
+        # device time of the individual steps of the timed region (HIP events between steps, rank 0): the spread behind the mean
+        "ms_per_step_median": round(per_step_ms[len(per_step_ms) // 2], 3), "ms_per_step_min": round(per_step_ms[0], 3),
+        "ms_per_step_max": round(per_step_ms[-1], 3),
+        "scaling": "strong" if strong else "weak",
+        "optimizer_steps_per_s": round(opt_steps_per_s, 3),
+        "vs_baseline": None, "dtype": "f32" if args.storage == "fp32" else "bf16 storage, f32 arithmetic", "data": "synthetic N(0,1) inputs/targets, reference-init weights",
+        "config": {"workload": "%s train step: FNOFactorized2DBlock(modes=%d,width=64,"
+                               "n_layers=%d,input_dim=3,share_weight,factor=4,weight_norm) %dx%d, fp32"
+                               % ("FNOPlus2DBlock (non-factorized ablation)" if args.plus else
+                                  "torus_li/markov/24_layers" if (G, args.layers, K) == (64, 24, 16) else "F-FNO",
+                                  K, args.layers, G, G),
+                   "per_gpu_batch": B, "global_batch": B * world, "parallelism": "dp%d" % world,
+                   "optimizer": "AdamW(lr 2.5e-3, wd 1e-4) + cosine warm-up, fused flat kernel",
+                   "collective": "1 x all_reduce(flat fp32 grads, %d floats) / step" % trainer.pflat.numel(),
+                   "arithmetic": "fp32 tensors and fp32-grade results throughout (forward <= 1e-5, gradients <= 5e-5 vs the fp64 "
+                                 "oracle at this geometry: tests/test_bench_geometry.py).  Matrix work on the low-precision "
+                                 "matrix cores through EXACT operand splits with fp32 accumulation: spectral branches and "
+                                 "Fourier-weight gradient as three bf16 planes / six v_mfma_f32_32x32x16_bf16 per product "
+                                 "block; feed-forward as " + (
+                                     "two fp16 planes (hi + lo / 2^11, both rounded to nearest: |error| <= 2^-24 |x|) / three "
+                                     "v_mfma_f32_32x32x16_f16 (measured 7.5e-8 rel-L2 vs fp64, fp32 MFMA: 1.5e-7)"
+                                     if trainer.engine.ff_split == "fp16x2" else "the same three-plane bf16 split"),
+                   "ff_split": trainer.engine.ff_split},
+        "samples_per_s": round(opt_steps_per_s * B * world, 1),
+        "final_loss": round(loss_val, 5), "git_head": git_head(), "lib_source_stamp": lib_source_stamp(),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -400,11 +491,17 @@ def main():
     ap.add_argument("--grid", type=int, default=64)
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--modes", type=int, default=16)
-    ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU-baseline train steps (0 disables the CPU leg)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the 256x256 and 64^3 secondary workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beyond the headline: instrumented pass, forward-only "
+                         "latencies, per-kernel replays and rooflines, arithmetic / bf16-storage variants, secondary workloads, "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, parameters and AdamW moments after the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="with --full: timed CPU-baseline train steps (0 disables the CPU leg)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the 256x256 and 64^3 secondary workloads")
     ap.add_argument("--storage", choices=["fp32", "bf16"], default="fp32",
-                    help="activation storage of the timed region (bf16: the storage twins -- a variant, not the parity path; the "
-                         "default run reports it beside the fp32 headline as `bf16_storage_variant`)")
+                    help="activation storage of the timed region (bf16: the storage twins -- a variant, not the parity path; "
+                         "--full reports it beside the fp32 headline as `bf16_storage_variant`)")
     ap.add_argument("--ff-split", choices=["fp16x2", "bf16x3"], default=None,
                     help="operand split of the feed-forward kernels (default: the engine's, fp16x2)")
     ap.add_argument("--staged", action="store_true", help="spectral branches through the three stage kernels (HBM spectra) instead of the fused tile")
@@ -415,6 +512,8 @@ def main():
                     help="the `value` of the same command at --gpus 1 (same per-GPU batch for weak scaling, same global batch for "
                          "strong scaling): the line then carries `efficiency_vs_n1` = value / (gpus x n1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as ONE command: re-launch ourselves as N ranks (one process per GPU) under
@@ -527,7 +626,17 @@ def main():
         torch.distributed.all_gather(allr, mine)
         per_rank = [dict(rank=r, step_ms_min=round(float(t[0]), 3), step_ms_median=round(float(t[1]), 3),
                          step_ms_max=round(float(t[2]), 3), region_wall_ms=round(float(t[3]), 3)) for r, t in enumerate(allr)]
-    # the instrumented pass: the same steps again (every rank runs them: the step holds a collective), brackets on rank 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, trainer)
+    if not args.full:
+        if rank == 0:
+            line = result_line(args, world, trainer, B, G, kw["modes"], elapsed, per_step_ms, loss_val)
+            line["distributed"] = distributed_info(args, world, rccl_world, rates(args, world, elapsed)[1], per_rank, None)
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+    # --full from here on.  The instrumented pass: the same steps again (every rank runs them: the step holds a collective), brackets on rank 0
     trainer.engine.timer = probe
     if probe:
         probe.sample = True
@@ -806,11 +915,7 @@ def main():
                                  f"launches per step), nothing subtracted; traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch from "
                                  f"profiles/pmc_traffic.json (separate rocprofv3 --pmc passes, gfx950 x2 correction on FETCH_SIZE), "
                                  f"taken at the git head named in traffic_source")
-        strong = bool(args.global_batch)
-        opt_steps_per_s = args.steps / elapsed                    # optimiser steps of the GLOBAL batch (B x world samples each)
-        # weak scaling: per-GPU-batch steps summed over ranks (= N x optimiser steps/s: what the driver divides by N x the
-        # one-GPU value); strong scaling (--global-batch): the global batch is fixed, so optimiser steps/s is the figure
-        steps_per_s = opt_steps_per_s if strong else world * args.steps / elapsed
+        opt_steps_per_s, steps_per_s = rates(args, world, elapsed)
         # the same step on the all-bf16x3 arithmetic (three bf16 planes, six MFMAs per product block everywhere: the round-1 /
         # early round-2 numerics), timed the same way right here, so that the line carries both
         variants = None
@@ -909,61 +1014,14 @@ def main():
             # the GPU is compared with (`speedup_vs_cpu_baseline`) is samples/s against the best form, under its own name
             cpu["best_form_steps_per_s_equivalent"] = round(forms[best] / B, 4)
             cpu["unit"] = "steps/s"
-        dist_info = None
-        if world > 1:
-            try:
-                ver = ".".join(str(v) for v in torch.cuda.nccl.version())
-            except Exception:  # noqa: BLE001
-                ver = None
-            dist_info = dict(world_size=torch.distributed.get_world_size(), world_size_counted_by_all_reduce=rccl_world,
-                             backend=torch.distributed.get_backend(), rccl_version=ver, hip=torch.version.hip,
-                             per_rank=per_rank, allreduce_us=allreduce_us,
-                             efficiency_vs_n1=(round(steps_per_s / (world * args.n1_steps_per_s), 4) if args.n1_steps_per_s > 0 else None),
-                             n1_steps_per_s=(args.n1_steps_per_s or None),
-                             launch="one process per GPU (torch.distributed.run; `python bench.py --gpus N` spawns them itself)")
-            if dist_info["backend"] == "nccl" and not ver:
-                raise SystemExit("backend nccl (= RCCL on ROCm) but torch reports no RCCL version: not an RCCL run, no line printed")
-        out = {
-            "metric": ("training-steps/sec (whole node), FNOPlus2DBlock %dL %dx%d modes %d" % (args.layers, G, G, K) if args.plus else
-                       "training-steps/sec (whole node), F-FNO 24L 64x64 torus (torus_li/markov/24_layers)"
-                       if (G, args.layers, K) == (64, 24, 16) else
-                       "training-steps/sec (whole node), F-FNO %dL %dx%d modes %d" % (args.layers, G, G, K)),
-            "value": round(steps_per_s, 3),
-            "unit": ("optimiser steps/s at global batch %d" % (B * world)) if strong else
-                    ("steps/s (per-GPU batch %d, summed over ranks)" % B),
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
-            # device time of the individual steps of the timed region (HIP events between steps, rank 0): the spread behind the mean
-            "ms_per_step_median": round(per_step_ms[len(per_step_ms) // 2], 3), "ms_per_step_min": round(per_step_ms[0], 3),
-            "ms_per_step_max": round(per_step_ms[-1], 3),
-            "scaling": "strong" if strong else "weak",
-            "optimizer_steps_per_s": round(opt_steps_per_s, 3),
-            "vs_baseline": None, "dtype": "f32" if args.storage == "fp32" else "bf16 storage, f32 arithmetic", "data": "synthetic N(0,1) inputs/targets, reference-init weights",
-            "config": {"workload": "%s train step: FNOFactorized2DBlock(modes=%d,width=64,"
-                                   "n_layers=%d,input_dim=3,share_weight,factor=4,weight_norm) %dx%d, fp32"
-                                   % ("FNOPlus2DBlock (non-factorized ablation)" if args.plus else
-                                      "torus_li/markov/24_layers" if (G, args.layers, K) == (64, 24, 16) else "F-FNO",
-                                      K, args.layers, G, G),
-                       "per_gpu_batch": B, "global_batch": B * world, "parallelism": "dp%d" % world,
-                       "optimizer": "AdamW(lr 2.5e-3, wd 1e-4) + cosine warm-up, fused flat kernel",
-                       "collective": "1 x all_reduce(flat fp32 grads, %d floats) / step" % trainer.pflat.numel(),
-                       "arithmetic": "fp32 tensors and fp32-grade results throughout (forward <= 1e-5, gradients <= 5e-5 vs the fp64 "
-                                     "oracle at this geometry: tests/test_bench_geometry.py).  Matrix work on the low-precision "
-                                     "matrix cores through EXACT operand splits with fp32 accumulation: spectral branches and "
-                                     "Fourier-weight gradient as three bf16 planes / six v_mfma_f32_32x32x16_bf16 per product "
-                                     "block; feed-forward as " + (
-                                         "two fp16 planes (hi + lo / 2^11, both rounded to nearest: |error| <= 2^-24 |x|) / three "
-                                         "v_mfma_f32_32x32x16_f16 (measured 7.5e-8 rel-L2 vs fp64, fp32 MFMA: 1.5e-7)"
-                                         if trainer.engine.ff_split == "fp16x2" else "the same three-plane bf16 split"),
-                       "ff_split": trainer.engine.ff_split},
-            "samples_per_s": round(opt_steps_per_s * B * world, 1), "ms_per_forward": round(ms_fwd, 3),
-            "ms_per_forward_batch1": round(ms_fwd_b1, 3),
+        out = result_line(args, world, trainer, B, G, K, elapsed, per_step_ms, loss_val)
+        out.update({
+            "ms_per_forward": round(ms_fwd, 3), "ms_per_forward_batch1": round(ms_fwd_b1, 3),
             "ms_per_forward_batch19": round(ms_fwd_b19, 3) if ms_fwd_b19 is not None else None,
-            "final_loss": round(loss_val, 5), "git_head": git_head(), "lib_source_stamp": lib_source_stamp(),
             "roofline": roofline, "roofline_forward": roofline_forward, "kernels": kernels, "power_note": power_note, "arithmetic_variants_steps_per_s": variants,
             "bf16_storage_variant": bf16_variant, "cpu_baseline": cpu,
-            "secondary": secondary, "distributed": dist_info,
-        }
+            "secondary": secondary, "distributed": distributed_info(args, world, rccl_world, steps_per_s, per_rank, allreduce_us),
+        })
         if cpu:
             # samples/s against the best CPU form (not against the large-batch one-pass figure, which a torch-CPU cliff depresses)
             out["speedup_vs_cpu_baseline"] = round(opt_steps_per_s * B * world / cpu["best_samples_per_s"], 1)

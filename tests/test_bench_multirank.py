@@ -21,7 +21,7 @@ def test_bench_multi_rank_dry_run(gpus, extra, scaling, gbatch):
     env = dict(os.environ, FFNO_BENCH_ONE_DEVICE="1")
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--cpu-steps", "0", "--no-secondary", "--n1-steps-per-s", "100"] + extra
+           "--full", "--cpu-steps", "0", "--no-secondary", "--n1-steps-per-s", "100"] + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -47,7 +47,7 @@ def test_bench_headline_line_carries_every_variant_leg():
     said so inside a nested dict.  A short headline run: both arithmetic variants and the bf16 storage variant must be numbers."""
     env = dict(os.environ)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--cpu-steps", "0", "--no-secondary"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--full", "--cpu-steps", "0", "--no-secondary"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

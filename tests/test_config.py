@@ -1,5 +1,8 @@
 """an experiment config in the reference's schema (torus_li/markov style: Hydra `_target_` nodes,
 `${get_method:...}` resolvers, functools.partial optimiser/scheduler factories) builds the HIP-backed routine."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
@@ -105,25 +108,31 @@ REFERENCE_CONFIGS = [
 ]
 
 
+def shipped_configs():
+    """{path under the reference's experiments/: YAML text} of all its config.yaml files, stored as test data
+    (tests/golden/reference_configs.npz, written by tools/make_config_fixture.py)."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_configs.npz"))
+    return dict(zip(z["paths"].tolist(), z["texts"].tolist()))
+
+
 @pytest.mark.parametrize("rel,routine_cls,attr,model_cls", REFERENCE_CONFIGS)
-def test_shipped_experiment_configs_build_unchanged(rel, routine_cls, attr, model_cls):
-    """The reference's own experiments/**/config.yaml files (read in place, build container only) instantiate the
+def test_shipped_experiment_configs_build_unchanged(rel, routine_cls, attr, model_cls, tmp_path):
+    """The reference's own experiments/**/config.yaml files (stored verbatim under tests/golden/) instantiate the
     native routine + operator without edits: same `_target_`s, kwargs, optimiser and schedule."""
-    import os
-    path = os.path.join(os.environ.get("FFNO_REFERENCE", "/root/reference"), "experiments", rel, "config.yaml")
-    if not os.path.exists(path):
-        pytest.skip("reference experiments are only present in the build container")
+    text = shipped_configs()[rel + "/config.yaml"]
+    path = tmp_path / "config.yaml"
+    path.write_text(text)
     import yaml
     from fourierflow_amd.config import build_routine, load_config
     # the non-factorized configs carry ~0.5 GB of [C, C, K, K, 2] weights per 24 layers: two layers are enough to check
     # that every constructor argument of the file arrives
     shrink = [f"routine.{attr}.n_layers=2"] if model_cls in ("FNOPlus2DBlock", "FNOMesh3D") else []
-    cfg = load_config(path, shrink)
+    cfg = load_config(str(path), shrink)
     routine = build_routine(cfg)
     assert type(routine).__name__ == routine_cls
     model = getattr(routine, attr)
     assert type(model).__name__ == model_cls
-    raw = yaml.safe_load(open(path))["routine"]
+    raw = yaml.safe_load(text)["routine"]
     for k, v in raw[attr].items():
         if not k.startswith("_") and isinstance(v, (int, float, bool)) and hasattr(model, k) and not (shrink and k == "n_layers"):
             assert getattr(model, k) == v, k
@@ -133,23 +142,21 @@ def test_shipped_experiment_configs_build_unchanged(rel, routine_cls, attr, mode
     assert {k: routine._sch_kw[k] for k in sch} == sch
 
 
-def test_every_shipped_ffno_config_builds():
-    """Sweep of the reference's 256 experiment configs (build container only): everything built on the F-FNO operators
+def test_every_shipped_ffno_config_builds(tmp_path):
+    """Sweep of the reference's 256 experiment configs (stored under tests/golden/): everything built on the F-FNO operators
     of SURVEY 8 instantiates unchanged; the rest fails LOUDLY with a reason from a short, explicit list."""
-    import glob
-    import os
-    root = os.path.join(os.environ.get("FFNO_REFERENCE", "/root/reference"), "experiments")
-    paths = sorted(glob.glob(os.path.join(root, "**", "config.yaml"), recursive=True))
-    if not paths:
-        pytest.skip("reference experiments are only present in the build container")
+    configs = shipped_configs()
+    assert len(configs) == 256, len(configs)
     from fourierflow_amd.config import build_routine, load_config
     known = ("FNOZongyi2DBlock", "width > 32", "FNOMesh2D", "FNOMesh3D", "PointCloud", "CNOFactorized", "IPhi",
              "only torch.optim.AdamW", "only CosineWithWarmupScheduler", "optax", "use_fourier_position",
              "MeshGraphNet", "LearnedInterpolator", "Grid2DRolloutExperiment")
     built, unexpected = 0, []
-    for p in paths:
+    for rel, text in configs.items():
+        p = tmp_path / "config.yaml"
+        p.write_text(text)
         try:
-            cfg = load_config(p)
+            cfg = load_config(str(p))
             node = cfg.get("routine", {})
             for key in ("conv", "model"):                 # one layer is enough to exercise every constructor argument
                 if isinstance(node.get(key), dict) and "n_layers" in node[key]:
@@ -158,8 +165,8 @@ def test_every_shipped_ffno_config_builds():
             built += 1
         except (NotImplementedError, ModuleNotFoundError) as e:
             if not any(k in str(e) for k in known):
-                unexpected.append((os.path.relpath(p, root), repr(e)))
+                unexpected.append((rel, repr(e)))
         except Exception as e:  # noqa: BLE001 - anything else is a loader bug
-            unexpected.append((os.path.relpath(p, root), repr(e)))
+            unexpected.append((rel, repr(e)))
     assert not unexpected, unexpected[:5]
     assert built >= 218, built

@@ -1,0 +1,34 @@
+"""Writes tests/golden/reference_configs.npz: the reference's experiments/**/config.yaml files as test data for
+tests/test_config.py (`paths`: path relative to experiments/, `texts`: the file's YAML text, both unicode arrays).
+
+Usage:  python tools/make_config_fixture.py REFERENCE_CHECKOUT
+"""
+import glob
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, "tests", "golden", "reference_configs.npz")
+
+
+def main():
+    if len(sys.argv) != 2:
+        raise SystemExit(__doc__)
+    exp = os.path.join(sys.argv[1], "experiments")
+    paths = sorted(os.path.relpath(p, exp) for p in glob.glob(os.path.join(exp, "**", "config.yaml"), recursive=True))
+    if not paths:
+        raise SystemExit(f"no experiments/**/config.yaml under {sys.argv[1]}")
+    texts = []
+    for p in paths:
+        with open(os.path.join(exp, p)) as f:
+            texts.append(f.read())
+    np.savez_compressed(OUT, paths=np.array(paths), texts=np.array(texts))
+    z = np.load(OUT)
+    assert z["paths"].tolist() == paths and z["texts"].tolist() == texts
+    print(f"{OUT}: {len(paths)} configs, {os.path.getsize(OUT)} bytes")
+
+
+if __name__ == "__main__":
+    main()
