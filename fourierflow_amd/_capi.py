@@ -251,6 +251,9 @@ SIGNATURES = {
     "ffno_adamw_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_adam_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_axpy": (I, [P, P, F, SZ, P]),
+    "ffno_nudft_supported": (I, [I, I, I]),
+    "ffno_nudft_modes": (I, [P, P, P, I, I, I, I, I, I, P]),
+    "ffno_nudft_points": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
 }
 
 

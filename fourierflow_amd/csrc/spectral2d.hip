@@ -283,3 +283,6 @@ extern "C" int ffno_fw3d_grad_reduce(const float* partial, float* g1, float* g2,
                 partial, G, C, K1, K2, K3, nsplit, accumulate);
     return s2d_status();
 }
+
+// the point-cloud F-FNO's non-uniform DFT (entry points ffno_nudft_*) lives in this translation unit
+#include "ffno_pointcloud.h"

@@ -291,3 +291,96 @@ def lp_rel_loss(pred, target):
     if pred.numel() != target.numel() or pred.shape[0] != target.shape[0]:
         raise ValueError(f"shape mismatch: {tuple(pred.shape)} vs {tuple(target.shape)}")
     return _LpRelLossFn.apply(pred.contiguous(), target.contiguous())
+
+
+def _nudft_check(xi, B, N, C, m1, m2):
+    _lib.require_device_tensor(xi, "xi")
+    if xi.dim() != 3 or xi.shape[0] != B or xi.shape[1] != N or xi.shape[2] != 2:
+        raise ValueError(f"xi: expected [B, N, 2] = [{B}, {N}, 2], got {tuple(xi.shape)}")
+    if not _lib.get_lib().ffno_nudft_supported(C, m1, m2):
+        raise ValueError(f"non-uniform DFT: modes ({m1}, {m2}) outside the compiled set (1..16 each)")
+
+
+class _PointFFT2dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, xi, m1, m2):
+        lib = _lib.get_lib()
+        B, C, N = u.shape
+        spec = torch.empty(B, C, 2 * m1, m2, 2, dtype=torch.float32, device=u.device)
+        _capi.check(lib.ffno_nudft_modes(_p(u), _p(xi), _p(spec), B, C, N, m1, m2, 0, _lib.current_stream(u.device)),
+                    "nudft_modes")
+        ctx.save_for_backward(u, xi)
+        ctx.cfg = (m1, m2)
+        return spec
+
+    @staticmethod
+    def backward(ctx, gspec):
+        u, xi = ctx.saved_tensors
+        m1, m2 = ctx.cfg
+        B, C, N = u.shape
+        gspec = gspec.contiguous()
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        dxi = torch.empty_like(xi) if ctx.needs_input_grad[1] else None
+        if du is not None or dxi is not None:
+            # the adjoint of fft2d is the modes -> points sum without the ifft2d factor: du = Re sum dY E, dxi from w = u
+            _capi.check(_lib.get_lib().ffno_nudft_points(_p(gspec), _p(xi), _p(u), _p(du), _p(dxi), B, C, N, m1, m2, 0, 0,
+                                                         _lib.current_stream(u.device)), "nudft_points (fft2d adjoint)")
+        return du, dxi, None, None
+
+
+class _PointIFFT2dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, xi):
+        lib = _lib.get_lib()
+        B, C, R, m2, _ = spec.shape
+        N = xi.shape[1]
+        out = torch.empty(B, C, N, dtype=torch.float32, device=spec.device)
+        _capi.check(lib.ffno_nudft_points(_p(spec), _p(xi), None, _p(out), None, B, C, N, R // 2, m2, 1, 0,
+                                          _lib.current_stream(spec.device)), "nudft_points")
+        ctx.save_for_backward(spec, xi)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        spec, xi = ctx.saved_tensors
+        B, C, R, m2, _ = spec.shape
+        N = xi.shape[1]
+        lib = _lib.get_lib()
+        st = _lib.current_stream(spec.device)
+        gout = gout.contiguous()
+        dspec = dxi = None
+        if ctx.needs_input_grad[0]:
+            dspec = torch.empty_like(spec)
+            _capi.check(lib.ffno_nudft_modes(_p(gout), _p(xi), _p(dspec), B, C, N, R // 2, m2, 1, st), "nudft_modes (ifft2d adjoint)")
+        if ctx.needs_input_grad[1]:
+            dxi = torch.empty_like(xi)
+            _capi.check(lib.ffno_nudft_points(_p(spec), _p(xi), _p(gout), None, _p(dxi), B, C, N, R // 2, m2, 1, 0, st),
+                        "nudft_points (ifft2d xi gradient)")
+        return dspec, dxi
+
+
+def point_fft2d(u, xi, modes1: int, modes2: int):
+    """``SpectralConv2d.fft2d(u, x_in)`` of the point-cloud F-FNO followed by its corner slicing (reference
+    modules/factorized_fno/point_cloud_2d.py:95-131, :54-62): u [B, C, N] on the points xi [B, N, 2] -> complex64
+    [B, C, 2 modes1, modes2], rows k1 = 0..modes1-1 then -modes1..-1, columns k2 = 0..modes2-1.  Differentiable in u and xi."""
+    _lib.require_device_tensor(u, "u")
+    if u.dim() != 3:
+        raise ValueError(f"u: expected [B, C, N], got {tuple(u.shape)}")
+    B, C, N = u.shape
+    _nudft_check(xi, B, N, C, modes1, modes2)
+    return torch.view_as_complex(_PointFFT2dFn.apply(u.contiguous(), xi.contiguous(), int(modes1), int(modes2)))
+
+
+def point_ifft2d(spec, xi):
+    """``SpectralConv2d.ifft2d(spec, x_out)`` of the point-cloud F-FNO (reference point_cloud_2d.py:133-159): complex64 spec
+    [B, C, 2 m1, m2] in the layout point_fft2d returns -> real [B, C, N] on the points xi [B, N, 2], including the reference's
+    `flip(-1, -2).conj()` completion of the negative-k2 half exactly as it computes it.  Differentiable in spec and xi."""
+    if not isinstance(spec, torch.Tensor) or spec.dtype != torch.complex64:
+        raise TypeError(f"spec: expected a complex64 tensor, got {getattr(spec, 'dtype', type(spec))}")
+    if spec.dim() != 4 or spec.shape[2] % 2:
+        raise ValueError(f"spec: expected [B, C, 2 m1, m2], got {tuple(spec.shape)}")
+    sr = torch.view_as_real(spec)
+    _lib.require_device_tensor(sr, "spec")
+    B, C, R, m2 = spec.shape
+    _nudft_check(xi, B, xi.shape[1] if xi.dim() == 3 else -1, C, R // 2, m2)
+    return _PointIFFT2dFn.apply(sr.contiguous(), xi.contiguous())

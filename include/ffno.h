@@ -924,6 +924,26 @@ typedef struct ffno_pad_desc {
 } ffno_pad_desc;
 int ffno_pad_copy(const ffno_pad_desc* descs, int n, int to_padded, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Non-uniform DFT of FNOFactorizedPointCloud2D (reference fourierflow/modules/factorized_fno/point_cloud_2d.py):
+ * SpectralConv2d.fft2d (:95-131) with the corner slicing of :54-62, and SpectralConv2d.ifft2d (:133-159) of the
+ * concatenated corners (:66-67).  Points xi[B][N][2] (float2, any real coordinates -- xi leaves [0,1]^2), point features
+ * [B][C][N], modes spec[B][C][2 m1][m2][2] (= view_as_real of complex64 [B, C, 2 m1, m2]); row r is k1 = r (r < m1) or
+ * r - 2 m1, column j is k2 = j.  With  E = exp(2 pi i (k1 xi_1 + j xi_2)) * q_j,  q_j = 1 + exp(2 pi i xi_1) for
+ * quirk = 1 and j >= 1, else 1  (q_j is the reference's `u_ft[..., 1:].flip(-1, -2).conj()` half, :153-154):
+ *   ffno_nudft_modes:   spec[b][c][r][j] = sum_n u[b][c][n] conj(E)
+ *       quirk 0: fft2d (no normalisation);  quirk 1: d ifft2d / d spec applied to dout (dV)
+ *   ffno_nudft_points:  out[b][c][n] = Re sum_{r,j} spec[b][c][r][j] E                     (out optional)
+ *       dxi[b][n][d] (+)= sum_c w[b][c][n] d out[b][c][n] / d xi_{n,d}                  (dxi optional, needs w; accumulate: +=)
+ *       quirk 1: ifft2d and its xi gradient (w = dout);  quirk 0: d fft2d / d u applied to dY (out = du; w = u gives dxi)
+ * m1, m2 <= 16 (ffno_nudft_supported).  fp32, deterministic (fixed summation order, no atomics).
+ * --------------------------------------------------------------------------------------------- */
+int ffno_nudft_supported(int C, int m1, int m2);
+int ffno_nudft_modes(const float* u, const float* xi, float* spec, int B, int C, int N, int m1, int m2, int quirk,
+                     void* stream);
+int ffno_nudft_points(const float* spec, const float* xi, const float* w, float* out, float* dxi, int B, int C, int N,
+                      int m1, int m2, int quirk, int accumulate, void* stream);
+
 /* small utilities used by the host driver */
 int ffno_axpy(float* y, const float* x, float alpha, size_t n, void* stream); /* y += alpha*x */
 
