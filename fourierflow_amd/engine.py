@@ -19,9 +19,10 @@ fp32 buffer (``gflat``) so the trainer can run ONE fused AdamW and ONE RCCL all-
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -37,6 +38,8 @@ _SUPPORTED_CH = {(64, 256), (64, 128), (32, 128), (32, 64)}
 X3_INTERLEAVE = 3
 # all-layers feed-forward weight-gradient launch: rounds of resident workgroups (FF_WGRAD_ROUNDS x CUs / L slices per layer)
 FF_WGRAD_ROUNDS = 3
+# workgroups of a Fourier-weight-gradient launch (slices x modes; with per-layer weights slices x modes x layers)
+FW_GRAD_WGS = 512
 
 
 def _fmix32(h: int) -> int:
@@ -63,6 +66,28 @@ def _p(t: Optional[torch.Tensor]):
 
 class _StackRetry(Exception):
     """The first persistent inference launch of a workspace reported an error: forward() starts over on the per-layer launches."""
+
+
+class _Plan(NamedTuple):
+    """What one forward pass (and the backward pass over it) runs, decided once before the layer loop."""
+    fused: List[bool]         # per axis: a fused branch kernel (else the stage kernels)
+    x3: List[bool]            # per axis: ... on the split (x3) fused kernels
+    x3fmt: List[int]          # per axis: format of the packed x3 weight sets (ffno.h FFNO_PLANES_*)
+    singles: List[int]        # axes that run on their own launches
+    pair: Optional[Tuple[int, int]]      # the two axes that share paired launches
+    conc: bool                # pair is not None
+    x3pair: bool              # the paired launches run on the split kernels
+    layer_calls: bool         # forward: one ffno_layer_fwd call per layer
+    bwd_layer_calls: bool     # backward: one ffno_layer_bwd call per layer (unless a timer is attached by then)
+    infer: bool               # the two-launch inference layer
+    infer_sr: bool            # ... self-ranged (no range words in this pass)
+    lazy: bool                # the feed-forward input sums are left to the deferred weight-gradient launch
+    bf16: bool                # bf16 activation storage
+    save: bool                # the pass saves for a backward pass
+
+
+# what forward(save_for_backward=True) hands to backward(): its input, the workspace it filled (and that workspace's key), its plan
+_Saved = collections.namedtuple("_Saved", "x B S ws ws_key plan")
 
 
 class _Linear:
@@ -207,6 +232,8 @@ class FFNOEngine:
         for names in self.fw_names:
             if names not in self._fw_sets:
                 self._fw_sets.append(names)
+        # weight set of every layer (0 without Fourier weights: no planes are read then)
+        self._fw_set_of = [self._fw_sets.index(names) for names in self.fw_names] or [0] * n_layers
 
         self.params: Dict[str, torch.Tensor] = {}
         self.device = None
@@ -216,53 +243,34 @@ class FFNOEngine:
         self._saved = None
         self._training = False
         self.use_fused = True   # fused A->B->C branch kernel when (C, K, L) fits its LDS tile; else 3 stage kernels
-        # operand split of those kernels: "fp16x2" (ffno_ffh_*: two fp16 planes, three MFMAs per product block -- half the matrix
-        # work; gradients are range-scaled by a device-resident power of two taken from the loss gradient) or "bf16x3"
-        # (ffno_ffx_*: three bf16 planes, six MFMAs, any fp32 range).  Both are fp32-grade (tests/test_kernels_ffh.py).
-        self.ff_split = os.environ.get("FFNO_FF_SPLIT", "fp16x2")
         # fused branches on the bf16 matrix cores at fp32 accuracy (spectral_x3.hip: 16 or 8 lines per workgroup -- the library
         # picks 8 while the launch still fits one round of workgroups -- packed pre-split weights) for the axes the library
         # takes (C = 64, K <= 16); 17..32 modes go through the split-bf16 stage kernels
         self.use_x3 = True
-        # the per-mode channel mix of the fused x3 kernel on "fp16x2" (three fp16 MFMAs per product block, weight packs two thirds
-        # the size; gradient passes hold the spectrum tile range-scaled like the feed-forward) or "bf16x3"
-        self.x3_mix_split = os.environ.get("FFNO_X3_MIX_SPLIT", "fp16x2")
-        self._x3_fmt = None
-        # operand split of the Fourier-weight-gradient contraction: None = follow x3_mix_split (fp16x2: three fp16 MFMAs per product,
-        # operands scaled from the range words of the layer inputs / data gradients; the bf16x3 launch runs on the 1400 W power cap)
-        self.fw_grad_split = os.environ.get("FFNO_FW_GRAD_SPLIT") or None
+        self._last_plan = None      # the plan of the last forward pass (paired_last, infer_last, _saved_x3, ...)
         self._dft_tabs = {}
         # feed-forward weight gradients of ALL layers as one launch after the backward loop (ffno_ffh_bwd_weights_partial_multi):
         # every layer keeps its own gradient buffer instead of the ping-pong pair; FF_WGRAD_ROUNDS x resident workgroups / L
         # slices per layer
-        self.ff_wgrad_deferred = os.environ.get("FFNO_FF_WGRAD_DEFERRED", "1") != "0"
+        self.ff_wgrad_deferred = True
         # ... and then the chain kernels leave the sums of their two input tensors unwritten (s_sum / db_sum NULL): every layer keeps
         # both branch outputs and both gradient buffers, the weight-gradient launch adds them while it stages its rows
         #   "s": the forward's input sums (the backward-data launch still writes its summed gradient: leaving that one out too was
         #   measured slower, round 4);  "0": none
-        self.ff_lazy_sums = os.environ.get("FFNO_FF_LAZY_SUMS", "s")
-        self.ff_schedule = int(os.environ.get("FFNO_FF_SCHED", "0"))      # ffno.h FFNO_FF_SCHED_* (0: the library's choice)
+        self.ff_lazy_sums = "s"
+        self.ff_schedule = 0      # ffno.h FFNO_FF_SCHED_* (0: the library's choice)
         # cap on the persistent workgroups of a feed-forward chain launch (ffno_ff_opts.max_workgroups and the field of the layer
         # descriptors; 0 = one per CU, the library's choice): for callers that share the device with another stream
         self.ff_max_workgroups = 0
         self.x3_min_lines = 1
         # workgroups (= partial slices) of the weight-gradient kernel: one per CU at width 64 (eight waves each), two per CU at
         # width 32 (four waves each: measured 157 -> 165 steps/s at 72^3 x 32 together with three chain workgroups per CU)
-        self.ff_wgrad_slices = int(os.environ.get("FFNO_FF_WGRAD_SLICES", "512" if width == 32 else "256"))
+        self.ff_wgrad_slices = 512 if width == 32 else 256
         # one C call per layer and direction (ffno_layer_fwd / ffno_layer_bwd: paired branches + feed-forward) instead of two /
         # three; per-kernel timing (a timer attached) needs the individual calls
         self.use_layer_calls = True
-        # forward passes that save nothing (predict / validation / rollout) through the two-launch INFERENCE layer (csrc/infer.hip:
-        # mixed spectra between the launches, no branch image in memory) where the library takes the shape and the launch is large
-        # enough to fill the chip; small launches (a rollout at batch 1) stay on the latency kernels of the training path
-        self.use_infer_layer = os.environ.get("FFNO_INFER_LAYER", "1") != "0"
         self.infer_self_range = True      # inference layers of axis length <= 64 scale every line from its own maximum (no range words)
-        self.use_infer_stack = os.environ.get("FFNO_INFER_STACK", "1") != "0"      # ... and run as one persistent launch where they can
         self.infer_stack_any_batch = False      # (see _stack_pays)
-        # <= 16 modes: the fused split kernels read their DFT-matrix fragments from the precomputed tables too (round 6; the many-mode
-        # and latency kernels always did) -- same values, results bit-identical; 0 = every wave rebuilds them from the twiddles
-        self.x3_dft_tables = os.environ.get("FFNO_X3_DFT_TABLES", "1") != "0"
-        self.x3_tile_lines = int(os.environ.get("FFNO_X3_TILE_LINES", "0"))      # ffno_fused_branch.tile_lines: 0 = the library's choice, 8 / 16
         self.infer_min_lines = None      # lines per axis pair from which the inference layer is used (None: more than 4 per CU)
         self._issue_stream = None   # torch stream object the next launches go to (None = current stream)
         self.timer = None   # optional KernelTimer (bench.py): HIP-event timing of individual launches
@@ -270,12 +278,22 @@ class FFNOEngine:
         # looked at one rebuild later -- with 1 (the default since round 4: three 3-us launches per step) an overflowing weight
         # is reported after at most one more optimiser step (include/ffno.h: |W| < 65504 is a hard precondition of the packs)
         self.weight_range_check_every = 1
-        # storage format of the activation tensors in HBM (include/ffno.h "Storage formats"): "fp32" = the parity path (the
-        # reference is precision: 32); "bf16" = the bf16 storage twins of the hot kernels -- half the activation bytes, results
-        # rounded to bf16 wherever a tensor is stored (a throughput variant with its own tolerance).  Available on the fused split
-        # kernels of every BASELINE shape (2-D width 64 up to 64 modes, 3-D width 32), 2-layer feed-forward, no fork heads /
-        # LayerNorm / dropout.
-        self.storage = os.environ.get("FFNO_STORAGE", "fp32")
+        self._read_environment()
+
+    def _read_environment(self):
+        """The switches of INTEGRATION.md, read once here (plain attributes after that)."""
+        env = os.environ
+        # operand split of the feed-forward kernels: "fp16x2" (ffno_ffh_*: two fp16 planes, three MFMAs per product block,
+        # operands range-scaled on the device) or "bf16x3" (ffno_ffx_*: three bf16 planes, six MFMAs, any fp32 range)
+        self.ff_split = env.get("FFNO_FF_SPLIT", "fp16x2")
+        self.x3_mix_split = env.get("FFNO_X3_MIX_SPLIT", "fp16x2")      # the same for the fused x3 mix and the Fourier-weight gradient
+        self.storage = env.get("FFNO_STORAGE", "fp32")      # activations in HBM (include/ffno.h "Storage formats"): "fp32" / "bf16"
+        # forward passes that save nothing through the two-launch inference layer (csrc/infer.hip) where it fills the chip ...
+        self.use_infer_layer = env.get("FFNO_INFER_LAYER", "1") != "0"
+        self.use_infer_stack = env.get("FFNO_INFER_STACK", "1") != "0"      # ... and the whole stack as one persistent launch
+        # memory cap of the deferred weight-gradient launch (2 L P C more words with lazy sums, 1.7 GB at the headline shape):
+        # beyond it the engine keeps the ping-pong pair and per-layer launches (ADVICE r04)
+        self.ff_defer_max_bytes = int(env.get("FFNO_FF_DEFER_MAX_BYTES", 16 << 30))
 
     def _bf16(self) -> bool:
         if self.storage not in ("fp32", "bf16"):
@@ -323,10 +341,8 @@ class FFNOEngine:
         if not fused:
             sv0 = save0 if save0 is not None else ws.SD
             sv1 = save1 if save1 is not None else ws.SD2
-            ba = _capi.FusedBranch(_p(src), _p(dst0), resid0, _p(sv0), _p(planes0), _p(self._twiddle(v0.L)),
-                                   v0.Bv, v0.Mv, v0.Nv, v0.K, v0.a01, acc0, 0, 0, None, rout if x3 else None)
-            bb = _capi.FusedBranch(_p(src), _p(dst1), resid1, _p(sv1), _p(planes1), _p(self._twiddle(v1.L)),
-                                   v1.Bv, v1.Mv, v1.Nv, v1.K, v1.a01, 0, 0, 0, None, rout if x3 else None)
+            ba = self._branch(v0, src, dst0, resid0, sv0, planes0, acc0, False, fwd, None, rout if x3 else None)
+            bb = self._branch(v1, src, dst1, resid1, sv1, planes1, 0, False, fwd, None, rout if x3 else None)
             fn = lib.ffno_spectral_x3_staged_pair if x3 else lib.ffno_spectral_staged_pair      # x3: planes are the packed sets
             self._k("spectral_staged_pair" + ("" if fwd else "(adj)"), fn, ctypes.byref(ba),
                     ctypes.byref(bb), _p(ws.SY), _p(ws.SY2), self.C, ck_f, ck_i, conj, st)
@@ -345,9 +361,9 @@ class FFNOEngine:
     def _branch(self, v, src, dst, resid, save, planes, acc, x3=False, fwd=True, rin=None, rout=None):
         """Branch descriptor; with fp16x2 packs the x3 kernel scales its spectrum tile from the range word of ``src``."""
         fmt = int(getattr(v, "x3fmt", 1)) if (x3 and planes is not None and self._x3_h2()) else 0      # ffno.h FFNO_PLANES_*
-        dft = self._dft_frags(v.L, v.K, fwd) if (fmt and (v.K > 16 or self.x3_dft_tables)) else None
+        dft = self._dft_frags(v.L, v.K, fwd) if fmt else None
         return _capi.FusedBranch(_p(src), _p(dst), resid, _p(save), _p(planes), _p(self._twiddle(v.L)), v.Bv, v.Mv, v.Nv, v.K,
-                                 v.a01, acc, fmt, int(self.x3_tile_lines), rin if fmt else None, rout, self._st(), 0, _p(dft))
+                                 v.a01, acc, fmt, 0, rin if fmt else None, rout, self._st(), 0, _p(dft))      # (tile_lines 0: library's)
 
     def _dft_frags(self, L: int, K: int, fwd: bool):
         """DFT-matrix fragment table of the many-mode fused kernel for (axis length, modes, direction): built once per engine and
@@ -374,23 +390,19 @@ class FFNOEngine:
         return bool((self._ffx() and self._h2()) or (self.use_x3 and self.spectral == "factorized" and self._x3_h2()))
 
     def _rw(self, ws, kind: str, l: int):
-        if not self._ranged():
-            return None
+        return ctypes.c_void_p(ws.RW.data_ptr() + 4 * (ws.rw_kinds[kind] * (self.L + 1) + l)) if self._ranged() else None
+
+    def _word(self, ws, kind: str, l: int):
         return ctypes.c_void_p(ws.RW.data_ptr() + 4 * (ws.rw_kinds[kind] * (self.L + 1) + l))
 
     def _fw_words(self, ws, l0: int):
         """Range words of the tensors whose spectra the Fourier-weight-gradient launch contracts, from layer l0 on: the layer inputs
         (kind x) and the feed-forward data gradients (kind d) -- (x words, d words) as device pointers, or (None, None): then the
         launch keeps the bf16x3 arithmetic (any range).  fp16x2 (three MFMAs per product instead of six) when the spectral kernels
-        run on fp16x2 packs, i.e. when every producer on the path records its maximum (`fw_grad_split`)."""
-        split = self.fw_grad_split or self.x3_mix_split
-        if split not in ("fp16x2", "bf16x3"):
-            raise ValueError("fw_grad_split must be 'fp16x2', 'bf16x3' or None (follow x3_mix_split), got %r" % (split,))
-        if not (split == "fp16x2" and self._ranged() and self.spectral == "factorized" and self.use_x3 and self._x3_h2()):
+        run on fp16x2 packs (x3_mix_split), i.e. when every producer on the path records its maximum."""
+        if not (self._x3_h2() and self._ranged() and self.spectral == "factorized" and self.use_x3):
             return None, None
-        base = ws.RW.data_ptr()
-        return (ctypes.c_void_p(base + 4 * (ws.rw_kinds["x"] * (self.L + 1) + l0)),
-                ctypes.c_void_p(base + 4 * (ws.rw_kinds["d"] * (self.L + 1) + l0)))
+        return self._word(ws, "x", l0), self._word(ws, "d", l0)
 
     def _fold(self, t, word, st):
         """Producers that do not record their output maximum themselves: one more pass over the tensor."""
@@ -428,26 +440,29 @@ class FFNOEngine:
 
     def _ffs_wgrad(self, s, g, l0, b0, part, P, nsplit, st, rs=None, rg=None):
         lib = _lib.get_lib()
+        args = (_p(s), _p(g), _p(l0.fx[0]), _p(b0), _p(l0.fx[2]), _p(part), P, self.C, self.H, nsplit)
         if self._h2():
-            self._k("ff_bwd_weights_partial", lib.ffno_ffh_bwd_weights_partial, _p(s), _p(g), _p(l0.fx[0]), _p(b0), _p(l0.fx[2]),
-                    _p(part), P, self.C, self.H, nsplit, rs, rg, self._st(), st)
+            self._k("ff_bwd_weights_partial", lib.ffno_ffh_bwd_weights_partial, *args, rs, rg, self._st(), st)
         else:
-            self._k("ff_bwd_weights_partial", lib.ffno_ffx_bwd_weights_partial, _p(s), _p(g), _p(l0.fx[0]), _p(b0), _p(l0.fx[2]),
-                    _p(part), P, self.C, self.H, nsplit, st)
+            self._k("ff_bwd_weights_partial", lib.ffno_ffx_bwd_weights_partial, *args, st)
 
     def _k(self, name, fn, *args):
         """Enqueue one C-ABI call; with a timer attached, bracket it with HIP events on the launch stream."""
         t = self.timer
         if t is not None and hasattr(t, "seen"):
             t.seen(name, fn, args)          # bench.py: capture (entry point, arguments) for replay timing
-        if t is not None and t.want(name):
-            t.start(name, self._issue_stream)
-            rc = fn(*args)
-            t.stop(name, self._issue_stream)
-        else:
-            rc = fn(*args)
+        rc = fn(*args) if t is None else self._timed(name, fn, *args)
         if rc != 0:
             _capi.check(rc, name)
+
+    def _timed(self, name, fn, *args) -> int:
+        t = self.timer
+        if t is None or not t.want(name):
+            return fn(*args)
+        t.start(name, self._issue_stream)
+        rc = fn(*args)
+        t.stop(name, self._issue_stream)
+        return rc
 
     # ------------------------------------------------------------------------------------------------
     def bind(self, params: Dict[str, torch.Tensor]):
@@ -561,18 +576,16 @@ class FFNOEngine:
                                                    (l0.weff, C_, 1, 2)), pk):
                     fdescs.append(_capi.FxPackDesc(src.data_ptr(), dst.data_ptr(), sh, sc, ty, 0))
             self._n_fx = len(fdescs)
-            arr = (_capi.FxPackDesc * len(fdescs))(*fdescs)
-            self._fx_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+            self._fx_dev = self._device_table(_capi.FxPackDesc, fdescs)
         self._n_tr = len(tdescs)
-        arr = (_capi.TrDesc * len(tdescs))(*tdescs)
-        self._tr_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+        self._tr_dev = self._device_table(_capi.TrDesc, tdescs)
         self._max_rows = max([l.rows for l in self.linears.values()])
-        if descs:
-            arr = (_capi.WnDesc * len(descs))(*descs)
-            raw = np.frombuffer(bytes(arr), dtype=np.uint8).copy()
-            self._desc_dev = torch.from_numpy(raw).to(self.device)
-        else:
-            self._desc_dev = None
+        self._desc_dev = self._device_table(_capi.WnDesc, descs) if descs else None
+
+    def _device_table(self, struct, items) -> torch.Tensor:
+        """A descriptor table (ctypes structs) as device bytes."""
+        arr = (struct * len(items))(*items)
+        return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
 
     def _twiddle(self, L: int) -> torch.Tensor:
         if L not in self._tw:
@@ -602,15 +615,16 @@ class FFNOEngine:
                 _View(B * X, Y, Z, 1, self.Ks[1], C),       # y: lines (b, x, z), stride Z*C
                 _View(B, X * Y, Z, 0, self.Ks[2], C)]       # z: contiguous lines (b, x, y)
 
-    def _sched_sig(self):
-        """Everything a workspace's buffers and schedule decisions (deferred weight-gradient launch, lazy input sums, slice counts)
-        are derived from besides the geometry: part of the workspace key, so an attribute switched on a live engine gets a
-        workspace laid out for it instead of decisions frozen for the old value."""
-        return (self._h2(), self._ranged(), bool(self.ff_wgrad_deferred), str(self.ff_lazy_sums), int(self.ff_wgrad_slices),
-                bool(self.use_x3), bool(self.use_fused))
+    def _workspace_key(self, B: int, S: Tuple[int, ...], save: bool):
+        """The geometry and everything a workspace's buffers and schedule decisions (deferred weight-gradient launch, lazy input
+        sums, slice counts) are derived from: an attribute switched on a live engine gets a workspace laid out for it instead of
+        decisions frozen for the old value."""
+        return (B, tuple(S), bool(save), self._ffx(), self._conc(), self.general_ff, self._bf16(),
+                (self._h2(), self._ranged(), bool(self.ff_wgrad_deferred), str(self.ff_lazy_sums), int(self.ff_wgrad_slices),
+                 bool(self.use_x3), bool(self.use_fused), int(self.ff_defer_max_bytes)))
 
     def _workspace(self, B: int, S: Tuple[int, ...], save: bool):
-        key = (B, tuple(S), bool(save), self._ffx(), self._conc(), self.general_ff, self._bf16(), self._sched_sig())
+        key = self._workspace_key(B, S, save)
         if self._ws_key == key:
             return self._ws
         cache = self.__dict__.setdefault("_ws_cache", {})   # a few recent geometries (train batch / validation batch /
@@ -628,11 +642,12 @@ class FFNOEngine:
         ws = type("WS", (), {})()
         ws.P, ws.P_in, ws.Sp = P, P_in, Sp
         ws.views = self._views(B, Sp)
-        ws.padmap = None
+        ws.padmap = ws.pm = None      # (pm: the argument the kernels take)
         if self.pad:
             s3 = (1,) * (3 - self.nd) + tuple(S)
             p3 = (1,) * (3 - self.nd) + tuple(Sp)
             ws.padmap = _capi.PadMap((ctypes.c_int32 * 3)(*s3), (ctypes.c_int32 * 3)(*p3))
+            ws.pm = ctypes.byref(ws.padmap)
         ws.X = torch.empty(P, C, **act)
         ws.Blast = torch.empty(P, C, **act)
         ws.Y = torch.empty(P_in * O, **f32)
@@ -694,11 +709,7 @@ class FFNOEngine:
             ws.defer_wgrad = bool(self.ff_wgrad_deferred and self._ffx() and self._h2() and self._ranged() and not self.share_fork
                                   and not self.use_fork and not self.layer_norm and not self.general_ff
                                   and (C, H) in ((64, 256), (32, 128)) and self.mode != "no-fourier")
-            # (what the deferred launch costs in memory: L - 1 more gradient buffers, and with lazy sums L more branch images --
-            #  2 L P C words together, 1.7 GB at the headline shape.  Beyond FFNO_FF_DEFER_MAX_BYTES (default 16 GiB of the 288)
-            #  the engine keeps the ping-pong pair and per-layer launches: ADVICE r04.)
-            extra = 2 * L * P * C * (2 if self._bf16() else 4)
-            if extra > int(os.environ.get("FFNO_FF_DEFER_MAX_BYTES", str(16 << 30))):
+            if 2 * L * P * C * (2 if self._bf16() else 4) > int(self.ff_defer_max_bytes):      # (its memory cost)
                 ws.defer_wgrad = False
             ws.G = [torch.empty(P, C, **act) for _ in range(L + 1 if ws.defer_wgrad else 2)]
             if self.ff_lazy_sums not in ("s", "0", ""):
@@ -719,8 +730,7 @@ class FFNOEngine:
                 njobs = L * (2 if self.use_fork else 1)
                 ws.ffparts = torch.empty(njobs, ws.ffpart.numel(), **f32)
                 ws.red_sig, ws.red_table = None, None
-            fwg = int(os.environ.get("FFNO_FW_GRAD_WGS", "512"))      # workgroups of a Fourier-weight-gradient launch (slices x modes)
-            ws.nsplit_fw = [max(1, min(max(1, fwg // v.K), (L * v.R + 63) // 64)) for v in ws.views]
+            ws.nsplit_fw = [max(1, min(max(1, FW_GRAD_WGS // v.K), (L * v.R + 63) // 64)) for v in ws.views]
             if self.spectral == "plus":
                 ws.nsplit_fw = [1]
             ws.fwpart = [[torch.empty(ws.nsplit_fw[w] * 2 * (ws.views[w].K2 if self.spectral == "plus" else ws.views[w].K)
@@ -737,20 +747,19 @@ class FFNOEngine:
             cache.pop(next(iter(cache)))
         return ws
 
-    def _forward_workspace(self, B: int, S: Tuple[int, ...]):
-        """The workspace the last ``forward(save_for_backward=True)`` filled.  A schedule / arithmetic attribute switched since then
-        (``ff_split``, ``x3_mix_split``, ``ff_wgrad_deferred``, ``ff_lazy_sums``, ``use_x3``, ``use_fused``, ``storage``, slice
-        counts) would select ANOTHER workspace -- whose saved tensors were never written: refuse instead of differentiating
-        uninitialised memory."""
-        ws = getattr(self, "_saved_ws", None)
-        if ws is None:
-            raise RuntimeError("backward() needs a preceding forward(save_for_backward=True)")
-        key = (B, tuple(S), True, self._ffx(), self._conc(), self.general_ff, self._bf16(), self._sched_sig())
-        if key != self._saved_ws_key:
+    def _saved_pass(self, what: str = "backward()") -> _Saved:
+        """What the last ``forward(save_for_backward=True)`` saved, the workspace it filled included.  A schedule / arithmetic
+        attribute switched since then (``ff_split``, ``x3_mix_split``, ``ff_wgrad_deferred``, ``ff_lazy_sums``, ``use_x3``,
+        ``use_fused``, ``storage``, slice counts) would select ANOTHER workspace -- and the kernels of this pass read some of them
+        as they are now: refuse instead of differentiating uninitialised memory."""
+        sv = self._saved
+        if sv is None:
+            raise RuntimeError(f"{what} needs a preceding forward(save_for_backward=True)")
+        if self._workspace_key(sv.B, sv.S, True) != sv.ws_key:
             raise RuntimeError("an engine attribute that shapes the workspace (ff_split / x3_mix_split / ff_wgrad_deferred / "
                                "ff_lazy_sums / ff_wgrad_slices / use_x3 / use_fused / storage) changed between forward() and "
                                "backward(): run the forward pass again")
-        return ws
+        return sv
 
     def weights_changed(self):
         """Tell the engine that parameter memory was written behind PyTorch's back (a raw-pointer kernel such as the fused
@@ -760,14 +769,14 @@ class FFNOEngine:
         call; writes through another alias of the same memory (a view of a flat buffer, ``p.data``'s source) do."""
         self._prep_sig = None
 
-    def _prepare_weights(self, st):
+    def _prepare_weights(self, st, x3fmt: List[int]):
         lib = _lib.get_lib()
         self._refresh_pointers()
         # derived operands only depend on the parameters and the arithmetic choices: an inference loop (rollout: 10-100 forwards
         # on the same weights) prepares them once -- five launches less per forward
         try:
             sig = (tuple((t.data_ptr(), t._version) for t in self.params.values()), self.ff_split, self.x3_mix_split,
-                   tuple(self._x3_fmt or ()), self.use_x3, getattr(st, "value", st))
+                   tuple(x3fmt), self.use_x3, getattr(st, "value", st))
         except RuntimeError:      # inference tensors (created under torch.inference_mode()) have no version counter:
             sig = None            # nothing to compare -- the operands are rebuilt by every forward, as before round 3
         if sig is not None and sig == getattr(self, "_prep_sig", None):
@@ -788,37 +797,34 @@ class FFNOEngine:
                 descs = [_capi.FwPackDesc(self.params[n].data_ptr(), self.planes[i][w][0].data_ptr(),
                                           self.planes[i][w][1].data_ptr(), self.Ks[w], int(self.spectral == "dct"))
                          for i, names in enumerate(self._fw_sets) for w, n in enumerate(names)]
-                arr = (_capi.FwPackDesc * len(descs))(*descs)
-                self._fwpack_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+                self._fwpack_dev = self._device_table(_capi.FwPackDesc, descs)
                 self._fwpack_sig, self._fwpack_n = sig, len(descs)
             self._k("fw_pack", lib.ffno_fw_pack_batched, _p(self._fwpack_dev), self._fwpack_n, self.C, max(self.Ks), st)
             if self.use_x3 and any(x is not None for row in self.xplanes for x in row):
-                fmt = self._x3_fmt or [0] * len(self.Ks)
-                sig = tuple((self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), fmt[w]) for i, row in enumerate(self.xplanes)
+                sig = tuple((self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), x3fmt[w]) for i, row in enumerate(self.xplanes)
                             for w, xp in enumerate(row) if xp is not None for d in range(2))
                 if sig != self._x3pack_sig:
-                    descs = [_capi.X3PackDesc(self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), self.Ks[w], fmt[w])
+                    descs = [_capi.X3PackDesc(self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), self.Ks[w], x3fmt[w])
                              for i, row in enumerate(self.xplanes) for w, xp in enumerate(row) if xp is not None
                              for d in range(2)]
-                    arr = (_capi.X3PackDesc * len(descs))(*descs)
-                    self._x3pack_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+                    self._x3pack_dev = self._device_table(_capi.X3PackDesc, descs)
                     self._x3pack_sig, self._x3pack_n = sig, len(descs)
                     self._x3pack_maxk = max(d.K for d in descs)
                 self._k("fw_pack_x3", lib.ffno_spectral_x3_pack, _p(self._x3pack_dev), self._x3pack_n, self.C, self._x3pack_maxk, st)
         o0, o1 = self.linears["out.0."], self.linears["out.1."]
         self._k("head_fold", lib.ffno_head_fold, _p(o0.weff), _p(self.params["out.0.bias"]), _p(o1.weff),
                 _p(self.params["out.1.bias"]), _p(self.fold), self.C, HEAD_DIM, self.O, st)
-        self._check_weight_range(st)
+        self._check_weight_range(st, x3fmt)
 
     # ---- the one operand the range words do not cover: the WEIGHTS inside the fp16x2 packs ---------------------------------
-    def _check_weight_range(self, st):
+    def _check_weight_range(self, st, x3fmt: List[int]):
         """Activations, spectra and gradients are brought into the half format's range per launch (range words).  Weights are
         packed as they are: one at or above 65504 would overflow its fp16 planes.  Every ``weight_range_check_every``-th time
         the derived operands are rebuilt, max |W| of everything that goes into an fp16x2 pack is folded on the device
         (ffno_amax) and copied to pinned host memory asynchronously; the value is looked at the next time round -- no
         synchronisation, the error arrives a few steps late but it arrives (the loss is NaN by then, and says why)."""
         every = int(self.weight_range_check_every)
-        fp16_ff, fp16_mix = self._ffx() and self._h2(), bool(self._x3_fmt and any(self._x3_fmt))
+        fp16_ff, fp16_mix = self._ffx() and self._h2(), any(x3fmt)
         if every <= 0 or not (fp16_ff or fp16_mix):
             return
         pend = self.__dict__.get("_wr_pending")
@@ -859,8 +865,7 @@ class FFNOEngine:
         # 4-us launches per step until round 5); the descriptor table is rebuilt when a tensor moved
         sig = tuple((t.data_ptr(), t.numel()) for t in srcs)
         if sig != self.__dict__.get("_wr_sig"):
-            arr = (_capi.AmaxDesc * len(sig))(*[_capi.AmaxDesc(ptr, n) for ptr, n in sig])
-            self._wr_table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+            self._wr_table = self._device_table(_capi.AmaxDesc, [_capi.AmaxDesc(ptr, n) for ptr, n in sig])
             self._wr_sig = sig
         self._k("amax", lib.ffno_amax_batched, _p(self._wr_table), len(sig), max(n for _, n in sig), _p(self._wr_word), st)
         ev = None
@@ -872,15 +877,11 @@ class FFNOEngine:
             self._wr_host.copy_(self._wr_word)
         self._wr_pending = (self._wr_host, ev)
 
-    def _ff_weights(self, l):
-        fp = self.ff_prefix[l]
+    def _ff_weights(self, l, prefixes=None):
+        """(linear 0, linear 1, bias 0, bias 1) of layer l's backcast (or, prefixes = fc_prefix, forecast) feed-forward."""
+        fp = (prefixes or self.ff_prefix)[l]
         l0, l1 = self.linears[fp + "layers.0.0."], self.linears[fp + "layers.1.0."]
         return l0, l1, self.params[fp + "layers.0.0.bias"], self.params[fp + "layers.1.0.bias"]
-
-    def _fc_weights(self, l):
-        fc = self.fc_prefix[l]
-        l0, l1 = self.linears[fc + "layers.0.0."], self.linears[fc + "layers.1.0."]
-        return l0, l1, self.params[fc + "layers.0.0.bias"], self.params[fc + "layers.1.0.bias"]
 
     # ---- feed-forward dispatch: split-bf16 kernels (ffx.hip) or the fp32-MFMA kernels (ff.hip) ---------------------
     def _ff_fwd(self, s, resid, l0, l1, b0, b1, out, hbuf, mask, P, st, rin=None, rout=None):
@@ -988,16 +989,10 @@ class FFNOEngine:
         if not (self.use_x3 and self.spectral == "factorized" and self.mode != "no-fourier"):
             return False
         P4 = 4 * self.C * max(u.Bv * u.Mv * u.Nv for u in views)       # 32-bit byte offsets inside the kernel
-        if not (v.R >= self.x3_min_lines and P4 < 2 ** 32 and lib.ffno_spectral_x3_supported(self.C, v.K, v.L)
-                and (self.mode != "full" or self.xplanes[0][w] is not None)):
-            return False
-        return True
+        return bool(v.R >= self.x3_min_lines and P4 < 2 ** 32 and lib.ffno_spectral_x3_supported(self.C, v.K, v.L)
+                    and (self.mode != "full" or self.xplanes[0][w] is not None))
 
-    def _use_x3(self, views, fused):
-        """Per axis: the split-bf16 fused branch instead of the fp32-MFMA one (same operator, same flags)."""
-        return [bool(fused[w] and self._x3_ok(w, v, views)) for w, v in enumerate(views)]
-
-    def _infer_ok(self, ws, B, conc, pair, singles, x3pair, fused) -> bool:
+    def _infer_ok(self, ws, conc, pair, singles, x3pair, fused) -> bool:
         """The two-launch inference layer (ffno_layer_infer) serves this forward: both axes of a 2-D layer in one paired launch of
         the fused split kernels with fp16x2 packs and <= 16 modes, width 64 / hidden 256 on the split-fp16 feed-forward, fp32
         activations, no fork heads / LayerNorm / dropout -- and enough lines to fill the chip."""
@@ -1036,7 +1031,7 @@ class FFNOEngine:
         tail = B % 32
         return tail == 0 or tail > 16
 
-    def _run_infer_stack(self, ws, pair, full, st) -> bool:
+    def _run_infer_stack(self, ws, pair, st) -> bool:
         """Enqueue ffno_infer_stack over ws.X (in place; the last layer's feed-forward output lands in ws.Blast).  False: not this
         shape / device, or the persistent launch reported a placement or barrier error (then it is switched off for this engine and
         the caller runs the per-layer launches)."""
@@ -1073,19 +1068,13 @@ class FFNOEngine:
             br.dft_frags = _p(self._dft_frags(v.L, v.K, True))
         rows = []
         for l in range(L):
-            si = self._fw_sets.index(self.fw_names[l]) if full else 0
+            si = self._fw_set_of[l]
             l0, l1, b0, b1 = self._ff_weights(l)
             rows.append(_capi.InferStackLayer(_p(self._planes_for(si, a, 0, True)), _p(self._planes_for(si, b, 0, True)), _p(l0.fx[0]),
                                               _p(b0), _p(l0.fx[1]), _p(b1)))
         arr = (_capi.InferStackLayer * L)(*rows)
         d = _capi.InferStackDesc(ba, bb, ctypes.cast(arr, ctypes.c_void_p), L, C, H, 0, _p(ws.Blast), _p(ws.stack_sync))
-        t = self.timer
-        if t is not None and t.want("infer_stack"):      # (bench.py: HIP events around the one launch)
-            t.start("infer_stack", self._issue_stream)
-            rc = lib.ffno_infer_stack(ctypes.byref(d), st)
-            t.stop("infer_stack", self._issue_stream)
-        else:
-            rc = lib.ffno_infer_stack(ctypes.byref(d), st)
+        rc = self._timed("infer_stack", lib.ffno_infer_stack, ctypes.byref(d), st)      # (bench.py: HIP events around it)
         if rc != 0:      # (e.g. the persistent launch was refused: the kernel does not fit once per CU on this device)
             self.use_infer_stack = False
             return False
@@ -1113,22 +1102,13 @@ class FFNOEngine:
                   x3: bool = False, rin=None, rout=None):
         """One spectral branch  dst (+)= [resid +] iDFT(mix(DFT(src)))  along view v (forward or adjoint);
         rin / rout = range words of src / dst."""
-        if not (fused and x3):
-            folded = self._spectral_plain(name, ws, v, src, dst, resid, save, planes, fwd, accumulate, fused, st, rout)
-            if not folded:
-                self._fold(dst, rout, st)       # the stage / DCT / 2-D kernels do not record their output maximum themselves
+        lib, C = _lib.get_lib(), self.C
+        ck_f, ck_i, conj = (0, 1, 0) if fwd else (1, 0, 1)
+        if fused and x3:
+            br = self._branch(v, src, dst, resid, save, planes, accumulate, True, fwd, rin, rout)
+            self._k(name, lib.ffno_spectral_x3, ctypes.byref(br), C, ck_f, ck_i, conj, st)
             return
-        br = self._branch(v, src, dst, resid, save, planes, accumulate, True, fwd, rin, rout)
-        ck_f, ck_i, conj = (0, 1, 0) if fwd else (1, 0, 1)
-        self._k(name, _lib.get_lib().ffno_spectral_x3, ctypes.byref(br), self.C, ck_f, ck_i, conj, st)
-
-    def _spectral_plain(self, name, ws, v: _View, src, dst, resid, save, planes, fwd: bool, accumulate: int, fused: bool, st,
-                        rout=None) -> bool:
-        """-> True when the kernel that ran folded max |dst| into ``rout`` itself."""
-        lib = _lib.get_lib()
-        C = self.C
         tw = self._twiddle(v.L)
-        ck_f, ck_i, conj = (0, 1, 0) if fwd else (1, 0, 1)
         if self.spectral == "plus":
             # rfft2 = last-axis DFT (K bins) then complex DFT along the first axis (2K retained rows); corner mix with the
             # (ky, kx') pairs as modes and the samples as rows; zero-padded inverse in the opposite order.  The adjoint
@@ -1142,25 +1122,24 @@ class FFNOEngine:
                     st)
             self._k("dft_inv", lib.ffno_dft_inv, _p(ws.SYb), _p(dst), resid, _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, 0, ck_i,
                     accumulate, st)
-            return
-        if self.spectral == "dct":       # DCT branch: the same transform pair serves the forward and the adjoint (orthonormal)
+        elif self.spectral == "dct":       # DCT branch: the same transform pair serves the forward and the adjoint (orthonormal)
             spec = save if save is not None else ws.SD
             self._k("dct_branch" + ("" if fwd else "(adj)"), lib.ffno_dct_branch, _p(src), _p(dst), resid, _p(spec), _p(ws.SY),
                     _p(planes), _p(self._twiddle(2 * v.L)), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, conj, accumulate, st)
-            return
-        if fused:
+        elif fused:      # (records its output maximum itself)
             self._k(name, lib.ffno_spectral_fused, _p(src), _p(dst), resid, _p(save), _p(planes), _p(tw),
                     v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_f, ck_i, conj, accumulate, rout, st)
-            return True
-        SD, SY = ws.SD, ws.SY
-        spec = save if save is not None else SD
-        self._k("dft_fwd", lib.ffno_dft_fwd, _p(src), _p(spec), _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_f, st)
-        y = spec
-        if planes is not None:
-            self._k("mode_mix", lib.ffno_mode_mix, _p(spec), _p(planes), _p(SY), v.R, C, v.K, conj, st)
-            y = SY
-        self._k("dft_inv", lib.ffno_dft_inv, _p(y), _p(dst), resid, _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_i,
-                accumulate, st)
+            return
+        else:
+            spec = save if save is not None else ws.SD
+            self._k("dft_fwd", lib.ffno_dft_fwd, _p(src), _p(spec), _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_f, st)
+            y = spec
+            if planes is not None:
+                self._k("mode_mix", lib.ffno_mode_mix, _p(spec), _p(planes), _p(ws.SY), v.R, C, v.K, conj, st)
+                y = ws.SY
+            self._k("dft_inv", lib.ffno_dft_inv, _p(y), _p(dst), resid, _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_i,
+                    accumulate, st)
+        self._fold(dst, rout, st)       # the stage / DCT / 2-D kernels do not record their output maximum themselves
 
     # ------------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, save_for_backward: bool, training: Optional[bool] = None, own_output: bool = True) -> torch.Tensor:
@@ -1168,6 +1147,20 @@ class FFNOEngine:
             return self._forward(x, save_for_backward, training, own_output)
         except _StackRetry:      # (the persistent inference launch is off now: the same pass on the per-layer launches)
             return self._forward(x, save_for_backward, training, own_output)
+
+    # ---- what the last forward pass ran (tests / bench.py); absent before the first one -------------------------------------
+    def _last(self, field: str):
+        if self._last_plan is None:
+            raise AttributeError(field)
+        return getattr(self._last_plan, field)
+
+    paired_last = property(lambda self: self._last("conc"))      # (bench.py: which algorithmic-work table applies)
+    infer_last = property(lambda self: self._last("infer"))
+    infer_self_ranged_last = property(lambda self: self._last("infer_sr"))
+    _saved_x3 = property(lambda self: (self._last("x3"), self._last("x3pair")))
+    _x3_fmt = property(lambda self: None if self._last_plan is None else self._last_plan.x3fmt)
+    _saved_lazy = property(lambda self: self._last("lazy"))
+    _saved_ws = property(lambda self: None if self._saved is None else self._saved.ws)      # (the workspace backward() will use)
 
     def _forward(self, x: torch.Tensor, save_for_backward: bool, training: Optional[bool] = None, own_output: bool = True) -> torch.Tensor:
         """x [B, *spatial, input_dim] fp32 on the device -> [B, *spatial, output_dim] (a fresh tensor).
@@ -1182,7 +1175,6 @@ class FFNOEngine:
         x = x.contiguous()
         B, S = x.shape[0], tuple(x.shape[1:-1])
         lib = _lib.get_lib()
-        C, H, L = self.C, self.H, self.L
         ws = self._workspace(B, S, save_for_backward)
         if self.mode != "no-fourier":
             for v in ws.views:
@@ -1190,12 +1182,41 @@ class FFNOEngine:
                     raise ValueError(f"modes={v.K} exceeds size//2+1 for an axis of length {v.L} "
                                      f"(the reference raises an einsum size error)")
         st = _lib.current_stream(self.device)
-        P = ws.P
         self._training = bool(save_for_backward if training is None else training)
         if self._training and (self.dropout > 0.0 or self.in_dropout > 0.0):
             self._drop_calls += 1
+        plan = self._last_plan = self._plan(ws, save_for_backward, st)
+        self._lift_fwd(x, ws, plan, st)
+        # the whole stack of self-ranged inference layers as ONE persistent launch (ffno_infer_stack: 64 x 64 images, batch x 8 = the CU
+        # count; the 8 workgroups of an image run both kernels of every layer as phases): no launch boundary, no chip-wide lock step
+        self.infer_stack_last = False
+        if (plan.infer_sr and self.use_infer_stack and (self.timer is None or getattr(self.timer, "allow_stack", False))
+                and self._run_infer_stack(ws, plan.pair, st)):
+            self.infer_stack_last = True
+        else:
+            layer = (self._fwd_layer_infer if plan.infer else self._fwd_layer_call if plan.layer_calls else self._fwd_layer_launches)
+            for l in range(self.L):
+                layer(ws, plan, l, st)
+        if self.use_fork:
+            torch.sum(ws.YL, dim=0, out=ws.Y)     # forecast = sum of the per-layer head outputs
+            self.forecast_list = [ws.YL[l].view(B, *S, self.O).clone() for l in range(self.L)]
+        else:
+            self._k("head_fwd", lib.ffno_head_fwd_bf16 if plan.bf16 else lib.ffno_head_fwd, _p(ws.Blast), _p(self.fold), _p(ws.Y),
+                    ws.P_in, self.C, self.O, 0, ws.pm, st)
+        # the workspace this pass filled (saved tensors, sign bits, range words): the backward pass and the diagnostic readers use
+        # THIS object -- an attribute switched between forward() and backward() changes the workspace key, and a freshly
+        # allocated workspace would hand them uninitialised memory (ADVICE r05, medium)
+        self._saved = _Saved(x, B, S, ws, self._ws_key, plan) if save_for_backward else None
+        y = ws.Y.view(B, *S, self.O)
+        return y.clone() if own_output else y
+
+    def _plan(self, ws, save: bool, st) -> _Plan:
+        """Which kernels this pass and the backward pass over it run; prepares the weight packs in the formats chosen here."""
+        lib = _lib.get_lib()
+        C, H = self.C, self.H
+        full = self.mode == "full"
         fused = self._can_fuse(ws.views)
-        x3 = self._use_x3(ws.views, fused)
+        x3 = [bool(fused[w] and self._x3_ok(w, v, ws.views)) for w, v in enumerate(ws.views)]      # ... on the split kernels
         # format of the packed x3 weight sets per axis: fp16x2 where the FUSED x3 kernel mixes with them (the stage kernels of
         # the 17..32-mode axes read bf16x3 packs)
         # ... and FFNO_PLANES_FP16X2_M16 (the 16-row mix) for the many-mode axes (width 64, 17..64 modes: 4-line tiles with 8 live mix
@@ -1203,11 +1224,10 @@ class FFNOEngine:
         # format and one tile height)
         many = [v.K > 16 for v in ws.views]
         m16 = bool(C == 64 and all(many) and len({v.K <= 32 for v in ws.views}) == 1)
-        self._x3_fmt = [(2 if (m16 and many[w]) else 1) if (self._x3_h2() and fused[w] and x3[w]) else 0 for w in range(len(ws.views))]
+        x3fmt = [(2 if (m16 and many[w]) else 1) if (self._x3_h2() and fused[w] and x3[w]) else 0 for w in range(len(ws.views))]
         for w, v in enumerate(ws.views):
-            v.x3fmt = self._x3_fmt[w]
-        self._prepare_weights(st)
-        full = self.mode == "full"
+            v.x3fmt = x3fmt[w]
+        self._prepare_weights(st, x3fmt)
         singles, pair = self._schedule(fused, ws.views) if self._conc() else (list(range(len(ws.views))), None)
         if pair is not None and fused[pair[0]] and not (x3[pair[0]] and x3[pair[1]]):
             # one fused launch for two axes needs ONE kernel family to take both shapes: either both on the split (x3) kernels
@@ -1224,18 +1244,18 @@ class FFNOEngine:
                 and 4 * C * max(v.Bv * v.Mv * v.Nv for v in ws.views) < 2 ** 32)
         layer_calls = bool(self.use_layer_calls and self.timer is None and conc and fused[pair[0]] and not self.use_fork
                            and not self.layer_norm)
-        infer = bool(not save_for_backward and self._infer_ok(ws, B, conc, pair, singles, x3pair, fused))
+        bwd_layer_calls = bool(self.use_layer_calls and conc and fused[pair[0]] and not singles and not self.use_fork
+                               and getattr(ws, "defer_reduce", False) and self.mode != "no-fourier" and not self.layer_norm)
+        infer = bool(not save and self._infer_ok(ws, conc, pair, singles, x3pair, fused))
         if infer and getattr(ws, "MIX", None) is None:
-            ws.MIX = [torch.empty(int(lib.ffno_infer_mix_bytes(C, ws.views[w].K, ws.views[w].R)) // 4, dtype=torch.int32, device=self.device)
-                      for w in pair]
-        self.infer_last = infer      # (tests / bench.py: which layer kernels the last forward ran)
+            ws.MIX = [torch.empty(int(lib.ffno_infer_mix_bytes(C, ws.views[w].K, ws.views[w].R)) // 4, dtype=torch.int32,
+                                  device=self.device) for w in pair]
         # self-ranged inference layers (axis lengths <= 64: ffno.h FFNO_BRANCH_SELF_RANGE): the first kernel scales every line from its
         # own maximum, so no launch of this forward has to fold a range word for it (lift, second kernel: no atomics, no fold barrier)
         infer_sr = bool(infer and self.infer_self_range and all(ws.views[w].L <= 64 for w in pair))
-        self.infer_self_ranged_last = infer_sr
         # both branch outputs of every layer are kept and the feed-forward does not write their sum (the deferred weight-gradient
-        # launch forms it): decided here, the backward pass follows (self._saved_lazy)
-        lazy = bool(save_for_backward and conc and getattr(ws, "lazy_sums", ""))
+        # launch forms it)
+        lazy = bool(save and conc and getattr(ws, "lazy_sums", ""))
         bf16 = self._bf16()
         if bf16 and not (all(fused) and all(x3) and self._h2() and self._x3_h2() and self._ffx() and self.spectral == "factorized"
                          and (C, H) in ((64, 256), (32, 128)) and full and not self.use_fork and not self.layer_norm
@@ -1244,165 +1264,142 @@ class FFNOEngine:
                 "storage='bf16' covers the fused split-kernel path of the factorized operators (2-D grids / meshes and the 3-D mesh: "
                 "width 64 with up to 64 modes or width 32 with up to 16, factor 4, mode='full', fp16x2 splits, 2-layer feed-forward "
                 "without fork heads / LayerNorm / dropout); this configuration runs with storage='fp32'")
+        return _Plan(fused, x3, x3fmt, singles, pair, conc, x3pair, layer_calls, bwd_layer_calls, infer, infer_sr, lazy, bf16, save)
+
+    def _lift_fwd(self, x, ws, plan: _Plan, st):
+        lib = _lib.get_lib()
         lin_in = self.linears["in_proj."]
-        pm = ctypes.byref(ws.padmap) if ws.padmap is not None else None
-        if pm is not None:
+        if ws.pm is not None:
             ws.X.zero_()     # F.pad(..., 0) of the lifted features (mesh_3d.py:165)
-        rw = self._rw
-        if self._ranged() and not infer_sr:
+        if self._ranged() and not plan.infer_sr:
             # the forward's words: layer inputs (x) and branch outputs (s) -- and, in the same launch, the words of the backward
             # pass that will follow this forward
             ws.RW.zero_()
             ws.rw_bwd_clean = True
         in_drop = self._training and self.in_dropout > 0.0
-        self._k("lift_fwd", lib.ffno_lift_fwd_bf16 if bf16 else lib.ffno_lift_fwd, _p(x), _p(lin_in.weff),
+        self._k("lift_fwd", lib.ffno_lift_fwd_bf16 if plan.bf16 else lib.ffno_lift_fwd, _p(x), _p(lin_in.weff),
                 _p(self.params["in_proj.bias"]), _p(ws.X), ws.P_in,
-                self.Cin, C, pm, None if (in_drop or infer_sr) else rw(ws, "x", 0), st)
+                self.Cin, self.C, ws.pm, None if (in_drop or plan.infer_sr) else self._rw(ws, "x", 0), st)
         if in_drop:      # x = self.drop(x) after in_proj (grid_2d.py:158): a regenerated mask over the lifted features
             self._in_drop_seed = _site_seed(self.drop_seed, self._drop_calls, 0xFFFF, 0, 2)
             self._k("in_dropout", lib.ffno_dropout, _p(ws.X), ws.X.numel(), self.in_dropout, self._in_drop_seed, st)
-            self._fold(ws.X, rw(ws, "x", 0), st)
-        # the whole stack of self-ranged inference layers as ONE persistent launch (ffno_infer_stack: 64 x 64 images, batch x 8 = the CU
-        # count; the 8 workgroups of an image run both kernels of every layer as phases): no launch boundary, no chip-wide lock step
-        self.infer_stack_last = False
-        if (infer_sr and self.use_infer_stack and (self.timer is None or getattr(self.timer, "allow_stack", False))
-                and self._run_infer_stack(ws, pair, full, st)):
-            self.infer_stack_last = True
-            n_loop = 0
+            self._fold(ws.X, self._rw(ws, "x", 0), st)
+
+    def _fwd_singles(self, ws, plan: _Plan, l: int, s_l, rx, rs_, st) -> int:
+        """s_l (+)= branch(x) of the axes that run on their own launches (stage-A spectra kept when training) -> how many."""
+        sv, full = (l if plan.save else 0), self.mode == "full"
+        for n, w in enumerate(plan.singles):
+            keep = ws.SXall[w][sv] if (full and (plan.save or not plan.fused[w])) else None
+            self._spectral("spectral_fused", ws, ws.views[w], ws.X, s_l, None, keep,
+                           self._planes_for(self._fw_set_of[l], w, 0, plan.x3[w]), True, int(n > 0), plan.fused[w], st,
+                           x3=plan.x3[w], rin=rx, rout=rs_)
+        return len(plan.singles)
+
+    def _fwd_layer_infer(self, ws, plan: _Plan, l: int, st):
+        """Layer l through the two-launch inference layer (ffno_layer_infer, or its two launches as two timed calls)."""
+        lib, C, H, last, si, (a, b) = _lib.get_lib(), self.C, self.H, l == self.L - 1, self._fw_set_of[l], plan.pair
+        rx, _, rxn = self._rw(ws, "x", l), self._rw(ws, "s", l), self._rw(ws, "x", l + 1)
+        l0, l1, b0, b1 = self._ff_weights(l)
+        ba = self._branch(ws.views[a], ws.X, ws.MIX[0], None, None, self._planes_for(si, a, 0, True), 0, True, True, rx, None)
+        bb = self._branch(ws.views[b], ws.X, ws.MIX[1], None, None, self._planes_for(si, b, 0, True), 0, True, True, rx, None)
+        if plan.infer_sr:
+            ba.flags = bb.flags = _capi.BRANCH_SELF_RANGE
+            ba.in_amax = bb.in_amax = None
+            rxn = None
+        out_l = ws.Blast if last else ws.X
+        if self.timer is None:
+            d = _capi.LayerInferDesc(ba, bb, X3_INTERLEAVE, 0, _p(l0.fx[0]), _p(b0), _p(l0.fx[1]), _p(b1),
+                                     None if last else _p(ws.X), _p(out_l), C, H, rxn)
+            self._k("layer_infer", lib.ffno_layer_infer, ctypes.byref(d), st)
+        else:       # (per-kernel timing: the two launches as two calls)
+            self._k("spectral_mix", lib.ffno_spectral_x3_mix_pair, ctypes.byref(ba), ctypes.byref(bb), C, X3_INTERLEAVE, st)
+            self._k("infer_ff", lib.ffno_infer_ff, ctypes.byref(ba), ctypes.byref(bb), _p(l0.fx[0]), _p(b0), _p(l0.fx[1]),
+                    _p(b1), None if last else _p(ws.X), _p(out_l), C, H, rxn, st)
+
+    def _fwd_layer_call(self, ws, plan: _Plan, l: int, st):
+        """Layer l as the axes that run on their own, then ONE call for the paired branches + feed-forward (ffno_layer_fwd)."""
+        save, lazy, x3pair, last = plan.save, plan.lazy, plan.x3pair, l == self.L - 1
+        sv = l if save else 0
+        s_l, si = ws.S[sv], self._fw_set_of[l]
+        a, b = plan.pair
+        rx, rs_, rxn = self._rw(ws, "x", l), self._rw(ws, "s", l), self._rw(ws, "x", l + 1)      # layer input, branch out, next
+        nwrit = self._fwd_singles(ws, plan, l, s_l, rx, rs_, st) if plan.singles else 0
+        keep_a, keep_b = (ws.SXall[a][sv], ws.SXall[b][sv]) if (save and self.mode == "full") else (None, None)
+        l0, l1, b0, b1 = self._ff_weights(l)
+        d = _capi.LayerFwdDesc(
+            self._branch(ws.views[a], ws.X, s_l, None, keep_a, self._planes_for(si, a, 0, x3pair), int(nwrit > 0), x3pair, True,
+                         rx, rs_),
+            self._branch(ws.views[b], ws.X, ws.TS[sv] if lazy else ws.T, None, keep_b, self._planes_for(si, b, 0, x3pair), 0, x3pair,
+                         True, rx, rs_),
+            int(x3pair), X3_INTERLEAVE, _p(l0.fx[0]), _p(b0), _p(l0.fx[1]), _p(b1),
+            _p(s_l) if (save and not lazy) else None, None if last else _p(ws.X), _p(ws.Blast if last else ws.X),
+            _p(ws.MASK[sv]) if save else None, ws.P, self.C, self.H, int(self._h2()),
+            int(self.ff_schedule), int(self.ff_max_workgroups), 0, 0, rxn)
+        self._k("layer_fwd", _lib.get_lib().ffno_layer_fwd, ctypes.byref(d), st)
+
+    def _fwd_layer_launches(self, ws, plan: _Plan, l: int, st):
+        """Layer l as individual launches: spectral branches (single, then paired), feed-forward, LayerNorm, fork head."""
+        lib, C, P, save, last = _lib.get_lib(), self.C, ws.P, plan.save, l == self.L - 1
+        sv = l if save else 0
+        s_l = ws.S[sv]
+        rx, rs_, rxn = self._rw(ws, "x", l), self._rw(ws, "s", l), self._rw(ws, "x", l + 1)      # layer input, branch out, next
+        t_l = (ws.TS[sv] if plan.lazy else ws.T) if plan.conc else None      # second branch output of a paired launch
+        if self.mode == "no-fourier":
+            s_l.copy_(ws.X)
+            self._fold(s_l, rs_, st)
         else:
-            n_loop = L
-        for l in range(n_loop):
-            sv = l if save_for_backward else 0
-            last = l == L - 1
-            s_l = ws.S[sv]
-            rx, rs_, rxn = rw(ws, "x", l), rw(ws, "s", l), rw(ws, "x", l + 1)
-            if self.mode == "no-fourier":
-                s_l.copy_(ws.X)
-                self._fold(s_l, rs_, st)
-            else:
-                si = self._fw_sets.index(self.fw_names[l]) if full else 0
-                nwrit = 0
-                for w in singles:
-                    v = ws.views[w]
-                    keep = ws.SXall[w][sv] if full else None     # stage-A spectrum (kept per layer when training)
-                    if fused[w] and not save_for_backward:
-                        keep = None
-                    self._spectral("spectral_fused", ws, v, ws.X, s_l, None, keep,
-                                   self._planes_for(si, w, 0, x3[w]), True, int(nwrit > 0), fused[w], st, x3=x3[w],
-                                   rin=rx, rout=rs_)
-                    nwrit += 1
-                if infer:
-                    a, b = pair
-                    l0, l1, b0, b1 = self._ff_weights(l)
-                    ba = self._branch(ws.views[a], ws.X, ws.MIX[0], None, None, self._planes_for(si, a, 0, True), 0, True, True, rx, None)
-                    bb = self._branch(ws.views[b], ws.X, ws.MIX[1], None, None, self._planes_for(si, b, 0, True), 0, True, True, rx, None)
-                    if infer_sr:
-                        ba.flags = bb.flags = _capi.BRANCH_SELF_RANGE
-                        ba.in_amax = bb.in_amax = None
-                        rxn = None
-                    out_l = ws.Blast if last else ws.X
-                    if self.timer is None:
-                        d = _capi.LayerInferDesc(ba, bb, X3_INTERLEAVE, 0, _p(l0.fx[0]), _p(b0), _p(l0.fx[1]), _p(b1),
-                                                 None if last else _p(ws.X), _p(out_l), C, H, rxn)
-                        self._k("layer_infer", lib.ffno_layer_infer, ctypes.byref(d), st)
-                    else:       # (per-kernel timing: the two launches as two calls)
-                        self._k("spectral_mix", lib.ffno_spectral_x3_mix_pair, ctypes.byref(ba), ctypes.byref(bb), C, X3_INTERLEAVE, st)
-                        self._k("infer_ff", lib.ffno_infer_ff, ctypes.byref(ba), ctypes.byref(bb), _p(l0.fx[0]), _p(b0), _p(l0.fx[1]),
-                                _p(b1), None if last else _p(ws.X), _p(out_l), C, H, rxn, st)
-                    continue
-                if conc:
-                    a, b = pair
-                    keep = [ws.SXall[w][sv] if (full and save_for_backward) else None for w in pair]
-                    t_l = ws.TS[sv] if lazy else ws.T
-                    if layer_calls:
-                        l0, l1, b0, b1 = self._ff_weights(l)
-                        d = _capi.LayerFwdDesc(
-                            self._branch(ws.views[a], ws.X, s_l, None, keep[0], self._planes_for(si, a, 0, x3pair), int(nwrit > 0),
-                                         x3pair, True, rx, rs_),
-                            self._branch(ws.views[b], ws.X, t_l, None, keep[1], self._planes_for(si, b, 0, x3pair), 0, x3pair, True,
-                                         rx, rs_),
-                            int(x3pair), X3_INTERLEAVE, _p(l0.fx[0]), _p(b0), _p(l0.fx[1]), _p(b1),
-                            _p(s_l) if (save_for_backward and not lazy) else None, None if last else _p(ws.X), _p(ws.Blast if last else ws.X),
-                            _p(ws.MASK[sv]) if save_for_backward else None, P, C, H, int(self._h2()),
-                            int(self.ff_schedule), int(self.ff_max_workgroups), 0, 0, rxn)
-                        self._k("layer_fwd", lib.ffno_layer_fwd, ctypes.byref(d), st)
-                        continue
-                    self._pair("spectral_fused", ws, ws.views[a], ws.views[b], ws.X, s_l, t_l, None, keep[0], keep[1],
-                               self._planes_for(si, a, 0, x3pair), self._planes_for(si, b, 0, x3pair), True, st,
-                               acc0=int(nwrit > 0), fused=fused[a], x3=x3pair, rin=rx, rout=rs_)
-            l0, l1, b0, b1 = self._ff_weights(l)
-            # FeedForward(layer_norm=True): the feed-forward writes its raw output, the LayerNorm kernel adds the residual
-            ff_out = ws.TL[sv] if self.layer_norm else (ws.Blast if last else ws.X)
-            ff_res = None if (self.layer_norm or last) else ws.X
-            ff_rout = None if self.layer_norm else rxn     # (LayerNorm: the next layer's input is the normalised tensor)
-            if conc:
-                self._ffs_fwd2(s_l, ws.TS[sv] if lazy else ws.T, s_l if (save_for_backward and not lazy) else None, ff_res, l0, b0, b1, ff_out,
-                               ws.MASK[sv] if save_for_backward else None, P, st, rs_, ff_rout)
-            elif self.use_fork and last:          # with fork heads the last layer's backcast only feeds the dead x_L
-                pass
-            elif self.general_ff:
-                self._ffg_fwd(ws, self.ff_prefix[l], "backcast", l, sv, s_l, ff_res, ff_out, P, st, ff_rout)
-            else:
-                self._ff_fwd(s_l, ff_res, l0, l1, b0, b1, ff_out,
-                             ws.Hbuf[sv] if save_for_backward else None, ws.MASK[sv] if save_for_backward else None, P, st,
-                             rs_, ff_rout)
-            if self.layer_norm and not (self.use_fork and last):
-                ln = self.ff_prefix[l] + f"layers.{self.n_ff - 1}.3."
-                self._k("layernorm_fwd", lib.ffno_layernorm_fwd, _p(ws.TL[sv]), _p(self.params[ln + "weight"]),
-                        _p(self.params[ln + "bias"]), None if last else _p(ws.X), _p(ws.Blast if last else ws.X), _p(ws.LNS[sv]),
-                        P, C, 1e-5, st)
-                if not last:
-                    self._fold(ws.X, rxn, st)
-            if self.use_fork:
-                c0, c1, cb0, cb1 = self._fc_weights(l)
-                f_raw = ws.TLF[sv] if self.layer_norm else ws.F[sv]
-                if self.general_ff:
-                    self._ffg_fwd(ws, self.fc_prefix[l], "forecast", l, sv, s_l, None, f_raw, P, st)
-                else:
-                    self._ff_fwd(s_l, None, c0, c1, cb0, cb1, f_raw, ws.HF[sv] if save_for_backward else None,
-                                 ws.MASKF[sv] if save_for_backward else None, P, st, rs_, None)
-                if self.layer_norm:
-                    ln = self.fc_prefix[l] + f"layers.{self.n_ff - 1}.3."
-                    self._k("layernorm_fwd", lib.ffno_layernorm_fwd, _p(f_raw), _p(self.params[ln + "weight"]),
-                            _p(self.params[ln + "bias"]), None, _p(ws.F[sv]), _p(ws.LNSF[sv]), P, C, 1e-5, st)
-                self._k("head_fwd", lib.ffno_head_fwd, _p(ws.F[sv]), _p(self.fold), _p(ws.YL[l]), ws.P_in, C, self.O, 0, pm, st)
+            nwrit = self._fwd_singles(ws, plan, l, s_l, rx, rs_, st)
+            if plan.conc:
+                si, (a, b), x3pair = self._fw_set_of[l], plan.pair, plan.x3pair
+                keep = [ws.SXall[w][sv] if (self.mode == "full" and save) else None for w in plan.pair]
+                self._pair("spectral_fused", ws, ws.views[a], ws.views[b], ws.X, s_l, t_l, None, keep[0], keep[1],
+                           self._planes_for(si, a, 0, x3pair), self._planes_for(si, b, 0, x3pair), True, st,
+                           acc0=int(nwrit > 0), fused=plan.fused[a], x3=x3pair, rin=rx, rout=rs_)
+        l0, l1, b0, b1 = self._ff_weights(l)
+        # FeedForward(layer_norm=True): the feed-forward writes its raw output, the LayerNorm kernel adds the residual
+        ff_out = ws.TL[sv] if self.layer_norm else (ws.Blast if last else ws.X)
+        ff_res = None if (self.layer_norm or last) else ws.X
+        ff_rout = None if self.layer_norm else rxn     # (LayerNorm: the next layer's input is the normalised tensor)
+        if plan.conc:
+            self._ffs_fwd2(s_l, t_l, s_l if (save and not plan.lazy) else None, ff_res, l0, b0, b1, ff_out,
+                           ws.MASK[sv] if save else None, P, st, rs_, ff_rout)
+        elif self.use_fork and last:          # with fork heads the last layer's backcast only feeds the dead x_L
+            pass
+        elif self.general_ff:
+            self._ffg_fwd(ws, self.ff_prefix[l], "backcast", l, sv, s_l, ff_res, ff_out, P, st, ff_rout)
+        else:
+            self._ff_fwd(s_l, ff_res, l0, l1, b0, b1, ff_out, ws.Hbuf[sv] if save else None, ws.MASK[sv] if save else None, P, st,
+                         rs_, ff_rout)
+        if self.layer_norm and not (self.use_fork and last):
+            ln = self.ff_prefix[l] + f"layers.{self.n_ff - 1}.3."
+            self._k("layernorm_fwd", lib.ffno_layernorm_fwd, _p(ws.TL[sv]), _p(self.params[ln + "weight"]),
+                    _p(self.params[ln + "bias"]), None if last else _p(ws.X), _p(ws.Blast if last else ws.X), _p(ws.LNS[sv]),
+                    P, C, 1e-5, st)
+            if not last:
+                self._fold(ws.X, rxn, st)
         if self.use_fork:
-            torch.sum(ws.YL, dim=0, out=ws.Y)     # forecast = sum of the per-layer head outputs
-            self.forecast_list = [ws.YL[l].view(B, *S, self.O).clone() for l in range(L)]
-        else:
-            self._k("head_fwd", lib.ffno_head_fwd_bf16 if bf16 else lib.ffno_head_fwd, _p(ws.Blast), _p(self.fold), _p(ws.Y),
-                    ws.P_in, C, self.O, 0, pm, st)
-        self._saved = (x, B, S, fused, conc) if save_for_backward else None
-        # the workspace this pass filled (saved tensors, sign bits, range words): the backward pass and the diagnostic readers use
-        # THIS object -- an attribute switched between forward() and backward() changes the workspace key, and a freshly
-        # allocated workspace would hand them uninitialised memory (ADVICE r05, medium)
-        self._saved_ws = ws if save_for_backward else None
-        self._saved_ws_key = self._ws_key if save_for_backward else None
-        self._saved_x3 = (x3, x3pair)
-        self._saved_sched = (singles, pair)
-        self._saved_lazy = lazy
-        self.paired_last = conc      # (bench.py: which algorithmic-work table applies)
-        y = ws.Y.view(B, *S, self.O)
-        return y.clone() if own_output else y
+            c0, c1, cb0, cb1 = self._ff_weights(l, self.fc_prefix)
+            f_raw = ws.TLF[sv] if self.layer_norm else ws.F[sv]
+            if self.general_ff:
+                self._ffg_fwd(ws, self.fc_prefix[l], "forecast", l, sv, s_l, None, f_raw, P, st)
+            else:
+                self._ff_fwd(s_l, None, c0, c1, cb0, cb1, f_raw, ws.HF[sv] if save else None, ws.MASKF[sv] if save else None, P, st,
+                             rs_, None)
+            if self.layer_norm:
+                ln = self.fc_prefix[l] + f"layers.{self.n_ff - 1}.3."
+                self._k("layernorm_fwd", lib.ffno_layernorm_fwd, _p(f_raw), _p(self.params[ln + "weight"]),
+                        _p(self.params[ln + "bias"]), None, _p(ws.F[sv]), _p(ws.LNSF[sv]), P, C, 1e-5, st)
+            self._k("head_fwd", lib.ffno_head_fwd, _p(ws.F[sv]), _p(self.fold), _p(ws.YL[l]), ws.P_in, C, self.O, 0, ws.pm, st)
 
     # ------------------------------------------------------------------------------------------------
     def backward(self, gy: torch.Tensor, need_dx: bool = False) -> torch.Tensor:
         """gy = dL/dout [B, *spatial, output_dim].  Fills and returns the flat gradient buffer ``gflat``
         (layout: ``param_names`` order; use ``grad_view(name)``).  ``need_dx``: also compute the gradient with respect to
         the input tensor (``self.dx``, [B, *spatial, input_dim]) -- what autograd of the reference module would hand upstream."""
-        if self._saved is None:
-            raise RuntimeError("backward() needs a preceding forward(save_for_backward=True)")
-        x, B, S, fused, conc = self._saved
-        x3, x3pair = self._saved_x3
-        singles, pair = self._saved_sched
+        saved = self._saved_pass()
         _lib.require_device_tensor(gy, "gy")
         gy = gy.contiguous()
-        lib = _lib.get_lib()
-        C, H, L = self.C, self.H, self.L
-        ws = self._forward_workspace(B, S)
-        lazy_s = bool(getattr(self, "_saved_lazy", False))            # forward input sums left to the weight-gradient launch
-        st = _lib.current_stream(self.device)
-        rw = self._rw
+        ws, plan, st, L = saved.ws, saved.plan, _lib.current_stream(self.device), self.L
         if self._ranged():
             # the backward's range words (g: running gradient, d: feed-forward data gradients, t / f: LayerNorm / fork heads):
             # every fp16x2 kernel of the pass scales its operands from the maximum its producer recorded -- per layer, on the
@@ -1410,183 +1407,195 @@ class FFNOEngine:
             if not getattr(ws, "rw_bwd_clean", False):      # (a second backward pass over the same forward)
                 ws.RW[2 * (L + 1):].zero_()
             ws.rw_bwd_clean = False
-        P = ws.P
-        full = self.mode == "full"
-        pm = ctypes.byref(ws.padmap) if ws.padmap is not None else None
-        o0, o1 = self.linears["out.0."], self.linears["out.1."]
-        gv = self.grad_view
-        have_g1 = False      # G1 holds the second adjoint branch's part of the running gradient (to be added to g_in)
-        cur = 0
-        if pm is not None:
-            (ws.GF if self.use_fork else ws.G[cur]).zero_()    # adjoint of the crop (mesh_3d.py:173)
-        if self.use_fork:
-            # every layer's f_l goes through the same head: d/df_l = gy . weff for all l (computed once), and the
-            # head-parameter reduction sums over layers
-            for l in range(L):
-                self._k("head_bwd", lib.ffno_head_bwd, _p(ws.F[l]), _p(gy), _p(self.fold), _p(ws.GF) if l == 0 else None,
-                        _p(ws.headpart), _p(ws.red if l == 0 else ws.redl), ws.P_in, C, self.O, ws.nsplit_head, pm,
-                        rw(ws, "f", 0) if l == 0 else None, st)
-                if l > 0:
-                    self._k("axpy", lib.ffno_axpy, _p(ws.red), _p(ws.redl), 1.0, self.O * (C + 1), st)
-        else:
-            self._k("head_bwd", lib.ffno_head_bwd_bf16 if self._bf16() else lib.ffno_head_bwd, _p(ws.Blast), _p(gy), _p(self.fold),
-                    _p(ws.G[cur]), _p(ws.headpart), _p(ws.red), ws.P_in, C, self.O, ws.nsplit_head, pm, rw(ws, "g", L - 1), st)
-        self._k("head_param_grads", lib.ffno_head_param_grads, _p(ws.red), _p(o0.weff), _p(self.params["out.0.bias"]),
-                _p(o1.weff), _p(o0.gweff), _p(gv("out.0.bias")), _p(o1.gweff), _p(gv("out.1.bias")), C, HEAD_DIM, self.O, 0, st)
-        if not self._ffx() and self._n_tr:
-            self._k("transpose_batched", lib.ffno_transpose_batched, _p(self._tr_dev), self._n_tr, max(C, H), max(C, H), st)
-        ff_seen = set()
+        self._head_bwd(ws, plan, gy, st)
         ws.red_jobs = []
-        nG = len(ws.G)
         # deferred weight-gradient launch: (s, summed gradient, packs, words, slices) of every layer, one launch after the loop
         # (paired launches or not: the airfoil mesh -- a 32-mode axis beside a 16-mode one, two launches per layer -- ran 24 per-layer
         #  weight-gradient launches of 56 us until round 5)
         ws.wg_jobs = [] if getattr(ws, "defer_wgrad", False) else None
-        if lazy_s and ws.wg_jobs is None:
+        if plan.lazy and ws.wg_jobs is None:
             raise RuntimeError("the forward pass left the feed-forward input sums to a deferred weight-gradient launch that this "
                                "backward pass cannot run")
-        layer_calls = bool(self.use_layer_calls and self.timer is None and conc and pair is not None and fused[pair[0]]
-                           and not singles and not self.use_fork and getattr(ws, "defer_reduce", False)
-                           and self.mode != "no-fourier" and not self.layer_norm)
+        layer = self._bwd_layer_call if (plan.bwd_layer_calls and self.timer is None) else self._bwd_layer_launches
+        ff_seen, cur = set(), 0
+        have_g1 = False      # G1 holds the second adjoint branch's part of the running gradient (to be added to g_in)
         for l in reversed(range(L)):
-            last = l == L - 1
-            l0, l1, _, _ = self._ff_weights(l)
-            fp = self.ff_prefix[l]
-            g_in, g_out, dh = ws.G[cur], ws.G[(cur + 1) % nG], ws.DH[l & 1]
-            g1_in = g1_out = getattr(ws, "G1", None)
             # words: gradient entering this layer, its feed-forward input, the data gradient, the gradient it hands on
-            rg, rs_, rd, rgo = rw(ws, "g", l), rw(ws, "s", l), rw(ws, "d", l), (rw(ws, "g", l - 1) if l > 0 else rw(ws, "g", L))
+            words = (self._rw(ws, "g", l), self._rw(ws, "s", l), self._rw(ws, "d", l),
+                     self._rw(ws, "g", l - 1) if l > 0 else self._rw(ws, "g", L))
             if self.use_fork:
-                c0, c1, _, _ = self._fc_weights(l)
-                fc = self.fc_prefix[l]
-                ds_f = ws.DS if last else ws.DSF     # last layer: the forecast path is the only contribution to ds
-                rf = rw(ws, "f", 0)
-                g_fc = ws.GF
-                if self.layer_norm:      # through the forecast block's LayerNorm first
-                    ln = fc + f"layers.{self.n_ff - 1}.3."
-                    self._k("layernorm_bwd", lib.ffno_layernorm_bwd, _p(ws.TLF[l]), _p(ws.LNSF[l]), _p(self.params[ln + "weight"]),
-                            _p(ws.GF), None, None, _p(ws.DTF), _p(ws.lnpart), _p(gv(ln + "weight")), _p(gv(ln + "bias")), P, C,
-                            int(fc in ff_seen), st)
-                    g_fc, rf = ws.DTF, rw(ws, "f", 1)
-                    self._fold(ws.DTF, rf, st)
-                if self.general_ff:
-                    self._ffg_bwd(ws, fc, "forecast", l, ws.S[l], g_fc, ds_f, int(fc in ff_seen), P, st, rd)
-                else:
-                    self._ff_bwd_data(g_fc, ws.MASKF[l], c0, c1, dh, ds_f, P, st, rf, rd)
-                    self._ff_bwd_weights(ws, ws.S[l], g_fc, ws.HF[l], dh, c0, c1, self.params[fc + "layers.0.0.bias"],
-                                         gv(fc + "layers.0.0.bias"), gv(fc + "layers.1.0.bias"), int(fc in ff_seen), P, st, rs_, rf)
-                ff_seen.add(fc)
-            if self.use_fork and last:
-                # x_L is never used with fork heads: the last backcast_ff gets a zero gradient
-                if fp not in ff_seen:
-                    for k in range(self.n_ff):
-                        gv(fp + f"layers.{k}.0.bias").zero_()
-                        self.linears[fp + f"layers.{k}.0."].gweff.zero_()
-                    if self.layer_norm:
-                        gv(fp + f"layers.{self.n_ff - 1}.3.weight").zero_()
-                        gv(fp + f"layers.{self.n_ff - 1}.3.bias").zero_()
-                    ff_seen.add(fp)
-                if self.mode == "no-fourier":
-                    g_out.copy_(ws.DS)
-                    self._fold(g_out, rgo, st)
-                else:
-                    si = self._fw_sets.index(self.fw_names[l]) if full else 0
-                    for w, v in enumerate(ws.views):
-                        keep = ws.SDall[w][l] if full else None
-                        self._spectral("spectral_fused(adj)", ws, v, ws.DS, g_out, None, keep,
-                                       self._planes_for(si, w, 1, x3[w]), False, int(w > 0), fused[w], st, x3=x3[w],
-                                       rin=rd, rout=rgo)
-                cur = (cur + 1) % nG
-                continue
-            if layer_calls:
-                # the whole layer backward in one call: FF data gradient (g_in (+)= G1), weight-gradient slices, adjoint pair
-                si = self._fw_sets.index(self.fw_names[l]) if full else 0
-                a, b = pair
-                part = ws.ffparts[len(ws.red_jobs)]
-                if ws.wg_jobs is not None:
-                    ws.wg_jobs.append((ws.S[l].data_ptr(), g_in.data_ptr(), l0.fx[0].data_ptr(),
-                                       self.params[fp + "layers.0.0.bias"].data_ptr(), l0.fx[2].data_ptr(), part.data_ptr(),
-                                       rs_.value, rg.value, ws.TS[l].data_ptr() if lazy_s else 0, 0))
-                d = _capi.LayerBwdDesc(
-                    self._branch(ws.views[a], ws.DS, g_out, None if last else _p(g_in), ws.SDall[a][l] if full else None,
-                                 self._planes_for(si, a, 1, x3pair), 0, x3pair, False, rd, rgo),
-                    self._branch(ws.views[b], ws.DS, g1_out, None, ws.SDall[b][l] if full else None,
-                                 self._planes_for(si, b, 1, x3pair), 0, x3pair, False, rd, rgo),
-                    int(x3pair), X3_INTERLEAVE, _p(g_in), _p(g1_in) if have_g1 else None, _p(g_in),
-                    _p(ws.MASK[l]),
-                    _p(l0.fx[2]), _p(l0.fx[3]), _p(ws.DS), _p(ws.S[l]), _p(l0.fx[0]), _p(self.params[fp + "layers.0.0.bias"]),
-                    None if ws.wg_jobs is not None else _p(part), ws.nsplit_ff, P, C, H, int(self._h2()),
-                    int(self.ff_schedule), int(self.ff_max_workgroups), 0, rg, rs_, rd)
-                self._k("layer_bwd", lib.ffno_layer_bwd, ctypes.byref(d), st)
-                ws.red_jobs.append((part.data_ptr(), l0.gweff.data_ptr(), l1.gweff.data_ptr(), gv(fp + "layers.0.0.bias").data_ptr(),
-                                    gv(fp + "layers.1.0.bias").data_ptr()))
-                ff_seen.add(fp)
-                have_g1 = True
-                cur = (cur + 1) % nG
-                continue
-            g_ff = g_in       # gradient w.r.t. the feed-forward output
+                self._bwd_forecast(ws, l, words, ff_seen, st)
+            if self.use_fork and l == L - 1:
+                self._bwd_fork_last(ws, plan, l, cur, words, ff_seen, st)
+            else:
+                have_g1 = layer(ws, plan, l, cur, have_g1, words, ff_seen, st)
+            cur = (cur + 1) % len(ws.G)
+        self._bwd_weight_grads(saved, cur, have_g1, need_dx, st)
+        return self.gflat
+
+    def _head_bwd(self, ws, plan: _Plan, gy, st):
+        lib, C, gv, pm, o0, o1 = _lib.get_lib(), self.C, self.grad_view, ws.pm, self.linears["out.0."], self.linears["out.1."]
+        if pm is not None:
+            (ws.GF if self.use_fork else ws.G[0]).zero_()    # adjoint of the crop (mesh_3d.py:173)
+        if self.use_fork:
+            # every layer's f_l goes through the same head: d/df_l = gy . weff for all l (computed once), and the
+            # head-parameter reduction sums over layers
+            for l in range(self.L):
+                self._k("head_bwd", lib.ffno_head_bwd, _p(ws.F[l]), _p(gy), _p(self.fold), _p(ws.GF) if l == 0 else None,
+                        _p(ws.headpart), _p(ws.red if l == 0 else ws.redl), ws.P_in, C, self.O, ws.nsplit_head, pm,
+                        self._rw(ws, "f", 0) if l == 0 else None, st)
+                if l > 0:
+                    self._k("axpy", lib.ffno_axpy, _p(ws.red), _p(ws.redl), 1.0, self.O * (C + 1), st)
+        else:
+            self._k("head_bwd", lib.ffno_head_bwd_bf16 if plan.bf16 else lib.ffno_head_bwd, _p(ws.Blast), _p(gy), _p(self.fold),
+                    _p(ws.G[0]), _p(ws.headpart), _p(ws.red), ws.P_in, C, self.O, ws.nsplit_head, pm, self._rw(ws, "g", self.L - 1), st)
+        self._k("head_param_grads", lib.ffno_head_param_grads, _p(ws.red), _p(o0.weff), _p(self.params["out.0.bias"]),
+                _p(o1.weff), _p(o0.gweff), _p(gv("out.0.bias")), _p(o1.gweff), _p(gv("out.1.bias")), C, HEAD_DIM, self.O, 0, st)
+        if not self._ffx() and self._n_tr:
+            self._k("transpose_batched", lib.ffno_transpose_batched, _p(self._tr_dev), self._n_tr, max(C, self.H), max(C, self.H), st)
+
+    def _bwd_forecast(self, ws, l: int, words, ff_seen, st):
+        """Fork heads: the forecast feed-forward of layer l (after its LayerNorm) -> its part of dL/ds."""
+        lib, C, P, gv, fc = _lib.get_lib(), self.C, ws.P, self.grad_view, self.fc_prefix[l]
+        _, rs_, rd, _ = words
+        c0, c1, _, _ = self._ff_weights(l, self.fc_prefix)
+        ds_f = ws.DS if l == self.L - 1 else ws.DSF     # last layer: the forecast path is the only contribution to ds
+        rf = self._rw(ws, "f", 0)
+        g_fc = ws.GF
+        if self.layer_norm:      # through the forecast block's LayerNorm first
+            ln = fc + f"layers.{self.n_ff - 1}.3."
+            self._k("layernorm_bwd", lib.ffno_layernorm_bwd, _p(ws.TLF[l]), _p(ws.LNSF[l]), _p(self.params[ln + "weight"]),
+                    _p(ws.GF), None, None, _p(ws.DTF), _p(ws.lnpart), _p(gv(ln + "weight")), _p(gv(ln + "bias")), P, C,
+                    int(fc in ff_seen), st)
+            g_fc, rf = ws.DTF, self._rw(ws, "f", 1)
+            self._fold(ws.DTF, rf, st)
+        if self.general_ff:
+            self._ffg_bwd(ws, fc, "forecast", l, ws.S[l], g_fc, ds_f, int(fc in ff_seen), P, st, rd)
+        else:
+            dh = ws.DH[l & 1]
+            self._ff_bwd_data(g_fc, ws.MASKF[l], c0, c1, dh, ds_f, P, st, rf, rd)
+            self._ff_bwd_weights(ws, ws.S[l], g_fc, ws.HF[l], dh, c0, c1, self.params[fc + "layers.0.0.bias"],
+                                 gv(fc + "layers.0.0.bias"), gv(fc + "layers.1.0.bias"), int(fc in ff_seen), P, st, rs_, rf)
+        ff_seen.add(fc)
+
+    def _bwd_fork_last(self, ws, plan: _Plan, l: int, cur: int, words, ff_seen, st):
+        """Fork heads, last layer: x_L is unused (zero backcast gradients), dL/ds comes from the forecast path alone."""
+        gv, fp = self.grad_view, self.ff_prefix[l]
+        _, _, rd, rgo = words
+        g_out = ws.G[(cur + 1) % len(ws.G)]
+        if fp not in ff_seen:
+            for k in range(self.n_ff):
+                gv(fp + f"layers.{k}.0.bias").zero_()
+                self.linears[fp + f"layers.{k}.0."].gweff.zero_()
             if self.layer_norm:
-                # through the LayerNorm first (it also folds in the second gradient buffer of a paired adjoint launch)
-                ln = fp + f"layers.{self.n_ff - 1}.3."
-                two = bool(conc and have_g1)
-                self._k("layernorm_bwd", lib.ffno_layernorm_bwd, _p(ws.TL[l]), _p(ws.LNS[l]), _p(self.params[ln + "weight"]),
-                        _p(g_in), _p(ws.G1) if two else None, _p(g_in) if two else None, _p(ws.DT), _p(ws.lnpart),
-                        _p(gv(ln + "weight")), _p(gv(ln + "bias")), P, C, int(fp in ff_seen), st)
-                g_ff = ws.DT
-                rg = rw(ws, "t", l)
-                self._fold(ws.DT, rg, st)
-            if conc:
-                # g_in (+)= G1 while it is staged; the sum is stored back for the weight gradient and the residual path
-                two = bool(have_g1 and not self.layer_norm)
-                self._ffs_bwd2(g_ff, g1_in if two else None, g_ff if two else None, ws.MASK[l], l0, ws.DS, P, st, rg, rd)
-                self._wg_second = ws.TS[l] if lazy_s else None
-            elif self.general_ff:
-                self._ffg_bwd(ws, fp, "backcast", l, ws.S[l], g_ff, ws.DS, int(fp in ff_seen), P, st, rd)
-            else:
-                self._ff_bwd_data(g_ff, ws.MASK[l], l0, l1, dh, ws.DS, P, st, rg, rd)
-                self._wg_second = None
-            if not self.general_ff:
-                self._ff_bwd_weights(ws, ws.S[l], g_ff, ws.Hbuf[l], dh, l0, l1, self.params[fp + "layers.0.0.bias"],
-                                     gv(fp + "layers.0.0.bias"), gv(fp + "layers.1.0.bias"), int(fp in ff_seen), P, st, rs_, rg)
+                gv(fp + f"layers.{self.n_ff - 1}.3.weight").zero_()
+                gv(fp + f"layers.{self.n_ff - 1}.3.bias").zero_()
             ff_seen.add(fp)
-            if self.use_fork:
-                self._k("axpy", lib.ffno_axpy, _p(ws.DS), _p(ws.DSF), 1.0, P * C, st)     # ds = ds(backcast) + ds(forecast)
-                self._fold(ws.DS, rd, st)     # (the word already holds both addends' maxima; the sum may exceed either)
-            if self.mode == "no-fourier":
-                if last:
-                    g_out.copy_(ws.DS)
-                else:
-                    torch.add(g_in, ws.DS, out=g_out)
-                self._fold(g_out, rgo, st)
-                cur = (cur + 1) % nG
-                continue
-            si = self._fw_sets.index(self.fw_names[l]) if full else 0
-            resid = None if last else _p(g_in)      # G_{l-1} = G_l (residual path) + adjoint terms; last layer: none
-            nwrit = 0
-            for w in singles:
-                v = ws.views[w]
-                keep = ws.SDall[w][l] if full else None   # dY of every layer is kept for the dW launch
-                self._spectral("spectral_fused(adj)", ws, v, ws.DS, g_out, resid if nwrit == 0 else None, keep,
-                               self._planes_for(si, w, 1, x3[w]), False, int(nwrit > 0), fused[w], st, x3=x3[w], rin=rd, rout=rgo)
-                nwrit += 1
-            if conc:
-                a, b = pair
-                self._pair("spectral_fused(adj)", ws, ws.views[a], ws.views[b], ws.DS, g_out, g1_out,
-                           resid if nwrit == 0 else None, ws.SDall[a][l] if full else None, ws.SDall[b][l] if full else None,
-                           self._planes_for(si, a, 1, x3pair), self._planes_for(si, b, 1, x3pair), False, st,
-                           acc0=int(nwrit > 0), fused=fused[a], x3=x3pair, rin=rd, rout=rgo,
-                           resid1=None)
-            have_g1 = conc
-            cur = (cur + 1) % nG
-        g_second = None           # second addend of the gradient that enters the lift (fp32 storage, no input gradient wanted:
-        if conc and have_g1:      # ffno_lift_bwd2 adds it while it stages its rows; else the sum is formed first)
-            g1_fin = ws.G1
-            if self._bf16():
-                ws.G[cur].add_(g1_fin)      # (a torch kernel on the same stream; rounds the sum to bf16 like every stored tensor)
-            elif need_dx or (self._training and self.in_dropout > 0.0):
-                self._k("axpy", lib.ffno_axpy, _p(ws.G[cur]), _p(g1_fin), 1.0, P * C, st)
+        if self.mode == "no-fourier":
+            g_out.copy_(ws.DS)
+            self._fold(g_out, rgo, st)
+            return
+        si = self._fw_set_of[l]
+        for w, v in enumerate(ws.views):
+            keep = ws.SDall[w][l] if self.mode == "full" else None
+            self._spectral("spectral_fused(adj)", ws, v, ws.DS, g_out, None, keep, self._planes_for(si, w, 1, plan.x3[w]), False,
+                           int(w > 0), plan.fused[w], st, x3=plan.x3[w], rin=rd, rout=rgo)
+
+    def _bwd_layer_call(self, ws, plan: _Plan, l: int, cur: int, have_g1: bool, words, ff_seen, st) -> bool:
+        """Layer l backward in one call (ffno_layer_bwd): FF data gradient (g_in (+)= G1), weight-gradient slices, adjoint pair."""
+        lib, gv, fp, last, full = _lib.get_lib(), self.grad_view, self.ff_prefix[l], l == self.L - 1, self.mode == "full"
+        g_in, g_out, g1, si, (a, b), x3pair = ws.G[cur], ws.G[(cur + 1) % len(ws.G)], ws.G1, self._fw_set_of[l], plan.pair, plan.x3pair
+        rg, rs_, rd, rgo = words
+        l0, l1, _, _ = self._ff_weights(l)
+        part = ws.ffparts[len(ws.red_jobs)]
+        if ws.wg_jobs is not None:
+            ws.wg_jobs.append((ws.S[l].data_ptr(), g_in.data_ptr(), l0.fx[0].data_ptr(),
+                               self.params[fp + "layers.0.0.bias"].data_ptr(), l0.fx[2].data_ptr(), part.data_ptr(),
+                               rs_.value, rg.value, ws.TS[l].data_ptr() if plan.lazy else 0, 0))
+        d = _capi.LayerBwdDesc(
+            self._branch(ws.views[a], ws.DS, g_out, None if last else _p(g_in), ws.SDall[a][l] if full else None,
+                         self._planes_for(si, a, 1, x3pair), 0, x3pair, False, rd, rgo),
+            self._branch(ws.views[b], ws.DS, g1, None, ws.SDall[b][l] if full else None,
+                         self._planes_for(si, b, 1, x3pair), 0, x3pair, False, rd, rgo),
+            int(x3pair), X3_INTERLEAVE, _p(g_in), _p(g1) if have_g1 else None, _p(g_in),
+            _p(ws.MASK[l]),
+            _p(l0.fx[2]), _p(l0.fx[3]), _p(ws.DS), _p(ws.S[l]), _p(l0.fx[0]), _p(self.params[fp + "layers.0.0.bias"]),
+            None if ws.wg_jobs is not None else _p(part), ws.nsplit_ff, ws.P, self.C, self.H, int(self._h2()),
+            int(self.ff_schedule), int(self.ff_max_workgroups), 0, rg, rs_, rd)
+        self._k("layer_bwd", lib.ffno_layer_bwd, ctypes.byref(d), st)
+        ws.red_jobs.append((part.data_ptr(), l0.gweff.data_ptr(), l1.gweff.data_ptr(), gv(fp + "layers.0.0.bias").data_ptr(),
+                            gv(fp + "layers.1.0.bias").data_ptr()))
+        ff_seen.add(fp)
+        return True
+
+    def _bwd_layer_launches(self, ws, plan: _Plan, l: int, cur: int, have_g1: bool, words, ff_seen, st) -> bool:
+        """Layer l backward as launches: LayerNorm, feed-forward (data, weights), adjoint branches.  -> G1 holds a part of g_out."""
+        lib, C, P, gv, fp, last = _lib.get_lib(), self.C, ws.P, self.grad_view, self.ff_prefix[l], l == self.L - 1
+        g_in, g_out, g1, dh = ws.G[cur], ws.G[(cur + 1) % len(ws.G)], getattr(ws, "G1", None), ws.DH[l & 1]
+        rg, rs_, rd, rgo, full = *words, self.mode == "full"
+        l0, l1, _, _ = self._ff_weights(l)
+        g_ff = g_in       # gradient w.r.t. the feed-forward output
+        if self.layer_norm:
+            # through the LayerNorm first (it also folds in the second gradient buffer of a paired adjoint launch)
+            ln = fp + f"layers.{self.n_ff - 1}.3."
+            two = bool(plan.conc and have_g1)
+            self._k("layernorm_bwd", lib.ffno_layernorm_bwd, _p(ws.TL[l]), _p(ws.LNS[l]), _p(self.params[ln + "weight"]),
+                    _p(g_in), _p(ws.G1) if two else None, _p(g_in) if two else None, _p(ws.DT), _p(ws.lnpart),
+                    _p(gv(ln + "weight")), _p(gv(ln + "bias")), P, C, int(fp in ff_seen), st)
+            g_ff = ws.DT
+            rg = self._rw(ws, "t", l)
+            self._fold(ws.DT, rg, st)
+        if plan.conc:
+            # g_in (+)= G1 while it is staged; the sum is stored back for the weight gradient and the residual path
+            two = bool(have_g1 and not self.layer_norm)
+            self._ffs_bwd2(g_ff, g1 if two else None, g_ff if two else None, ws.MASK[l], l0, ws.DS, P, st, rg, rd)
+            self._wg_second = ws.TS[l] if plan.lazy else None
+        elif self.general_ff:
+            self._ffg_bwd(ws, fp, "backcast", l, ws.S[l], g_ff, ws.DS, int(fp in ff_seen), P, st, rd)
+        else:
+            self._ff_bwd_data(g_ff, ws.MASK[l], l0, l1, dh, ws.DS, P, st, rg, rd)
+            self._wg_second = None
+        if not self.general_ff:
+            self._ff_bwd_weights(ws, ws.S[l], g_ff, ws.Hbuf[l], dh, l0, l1, self.params[fp + "layers.0.0.bias"],
+                                 gv(fp + "layers.0.0.bias"), gv(fp + "layers.1.0.bias"), int(fp in ff_seen), P, st, rs_, rg)
+        ff_seen.add(fp)
+        if self.use_fork:
+            self._k("axpy", lib.ffno_axpy, _p(ws.DS), _p(ws.DSF), 1.0, P * C, st)     # ds = ds(backcast) + ds(forecast)
+            self._fold(ws.DS, rd, st)     # (the word already holds both addends' maxima; the sum may exceed either)
+        if self.mode == "no-fourier":
+            if last:
+                g_out.copy_(ws.DS)
             else:
-                g_second = g1_fin
+                torch.add(g_in, ws.DS, out=g_out)
+            self._fold(g_out, rgo, st)
+            return have_g1
+        si = self._fw_set_of[l]
+        resid = None if last else _p(g_in)      # G_{l-1} = G_l (residual path) + adjoint terms; last layer: none
+        for n, w in enumerate(plan.singles):
+            keep = ws.SDall[w][l] if full else None   # dY of every layer is kept for the dW launch
+            self._spectral("spectral_fused(adj)", ws, ws.views[w], ws.DS, g_out, resid if n == 0 else None, keep,
+                           self._planes_for(si, w, 1, plan.x3[w]), False, int(n > 0), plan.fused[w], st, x3=plan.x3[w], rin=rd,
+                           rout=rgo)
+        if plan.conc:
+            a, b = plan.pair
+            self._pair("spectral_fused(adj)", ws, ws.views[a], ws.views[b], ws.DS, g_out, g1,
+                       None if plan.singles else resid, ws.SDall[a][l] if full else None, ws.SDall[b][l] if full else None,
+                       self._planes_for(si, a, 1, plan.x3pair), self._planes_for(si, b, 1, plan.x3pair), False, st,
+                       acc0=int(bool(plan.singles)), fused=plan.fused[a], x3=plan.x3pair, rin=rd, rout=rgo)
+        return plan.conc
+
+    def _bwd_weight_grads(self, saved: _Saved, cur: int, have_g1: bool, need_dx: bool, st):
+        """After the layer loop: deferred feed-forward weight gradients, lift backward (dL/dx), Fourier weights, weight norm."""
+        lib, ws, plan, x = _lib.get_lib(), saved.ws, saved.plan, saved.x
+        C, H, L, P, gv, pm = self.C, self.H, self.L, ws.P, self.grad_view, ws.pm
+        g_second = None                # second addend of the gradient that enters the lift (fp32 storage, no input gradient wanted:
+        if plan.conc and have_g1:      # ffno_lift_bwd2 adds it while it stages its rows; else the sum is formed first)
+            if plan.bf16:
+                ws.G[cur].add_(ws.G1)      # (a torch kernel on the same stream; rounds the sum to bf16 like every stored tensor)
+            elif need_dx or (self._training and self.in_dropout > 0.0):
+                self._k("axpy", lib.ffno_axpy, _p(ws.G[cur]), _p(ws.G1), 1.0, P * C, st)
+            else:
+                g_second = ws.G1
         nsl = ws.nsplit_ff
         if ws.wg_jobs:
             nsl = ws.nsplit_ffm
@@ -1595,12 +1604,11 @@ class FFNOEngine:
                 ws.wg_table = (_capi.FfWgDesc * len(sig))(*[_capi.FfWgDesc(*j) for j in sig])
                 ws.wg_sig = sig
             self._k("ff_bwd_weights_partial", lib.ffno_ffh_bwd_weights_partial_multi, ws.wg_table, len(sig), P, C, H, nsl,
-                    self._st(), int(lazy_s), st)
+                    self._st(), int(plan.lazy), st)
         if getattr(ws, "defer_reduce", False) and ws.red_jobs:
             sig = tuple(ws.red_jobs)
             if sig != ws.red_sig:       # pointers only change when parameters are re-bound or the workspace is rebuilt
-                arr = (_capi.FxRedDesc * len(sig))(*[_capi.FxRedDesc(*j) for j in sig])
-                ws.red_table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+                ws.red_table = self._device_table(_capi.FxRedDesc, [_capi.FxRedDesc(*j) for j in sig])
                 ws.red_sig = sig
             self._k("ff_bwd_weights_reduce", lib.ffno_ffx_bwd_weights_reduce_batched, _p(ws.red_table), len(sig), C, H,
                     nsl, st)
@@ -1612,23 +1620,21 @@ class FFNOEngine:
             self._k("lift_bwd", lib.ffno_lift_bwd2, _p(x), _p(g_fin), _p(g_second), _p(ws.liftpart), _p(lin_in.gweff),
                     _p(gv("in_proj.bias")), ws.P_in, self.Cin, C, ws.nsplit_lift, 0, pm, st)
         else:
-            self._k("lift_bwd", lib.ffno_lift_bwd_bf16 if self._bf16() else lib.ffno_lift_bwd, _p(x), _p(g_fin), _p(ws.liftpart),
+            self._k("lift_bwd", lib.ffno_lift_bwd_bf16 if plan.bf16 else lib.ffno_lift_bwd, _p(x), _p(g_fin), _p(ws.liftpart),
                     _p(lin_in.gweff), _p(gv("in_proj.bias")), ws.P_in, self.Cin, C, ws.nsplit_lift, 0, pm, st)
         self.dx = None
         if need_dx:
-            self.dx = torch.empty(B, *S, self.Cin, dtype=torch.float32, device=self.device)
-            g_dx = g_fin.float() if self._bf16() else g_fin      # (the input gradient is an fp32 tensor of the caller)
+            self.dx = torch.empty(saved.B, *saved.S, self.Cin, dtype=torch.float32, device=self.device)
+            g_dx = g_fin.float() if plan.bf16 else g_fin      # (the input gradient is an fp32 tensor of the caller)
             self._k("lift_bwd_data", lib.ffno_lift_bwd_data, _p(g_dx), _p(lin_in.weff), _p(self.dx), ws.P_in, self.Cin, C, pm, st)
         multi = self.spectral != "plus" and len(self._fw_sets) == L and L > 1      # per-layer weights: one launch per axis
         if multi:
             real = int(self.spectral == "dct")
-            for w in range(len(ws.views)):
-                v = ws.views[w]
+            for w, v in enumerate(ws.views):
                 # slices per (layer, mode): the grid is slices x modes x LAYERS here, so the per-axis count of the shared-weight
                 # launch (512 / K) would make 12 288 workgroups of 37 lines each at the airfoil shape and 384 MB of partial
                 # slices for the reduce launch to read back; ~512 workgroups in all are enough
-                fwg = int(os.environ.get("FFNO_FW_GRAD_WGS", "512"))      # the knob that sizes ws.nsplit_fw, here per (layer, mode)
-                nsf = max(1, min(-(-fwg // (v.K * L)), (v.R + 63) // 64))
+                nsf = max(1, min(-(-FW_GRAD_WGS // (v.K * L)), (v.R + 63) // 64))
                 pstride = nsf * 2 * v.K * C * C
                 if getattr(ws, "fwpart_multi", None) is None:
                     ws.fwpart_multi, ws.fwgrad_tab, ws.fwgrad_sig = {}, {}, {}
@@ -1644,7 +1650,7 @@ class FFNOEngine:
                 self._k("fw_grad_reduce", lib.ffno_fw_grad_reduce_multi, _p(ws.fwpart_multi[w]), _p(ws.fwgrad_tab[w]), L, C, v.K,
                         nsf, pstride, 0, real, st)
         for si, names in enumerate(self._fw_sets if not multi else []):
-            layers = [l for l in range(L) if self.fw_names[l] == names]
+            layers = [l for l in range(L) if self._fw_set_of[l] == si]
             l0_, nl = layers[0], len(layers)
             assert layers == list(range(l0_, l0_ + nl))
             if self.spectral == "plus":
@@ -1664,23 +1670,19 @@ class FFNOEngine:
                 self._k("fw_grad_reduce", reduce, _p(ws.fwpart[si][w]), _p(gv(n)), C, v.K, ws.nsplit_fw[w], 0, st)
         if self._desc_dev is not None:
             self._k("weightnorm_bwd", lib.ffno_weightnorm_bwd, _p(self._desc_dev), self._n_desc, self._max_rows, st)
-        return self.gflat
 
 
     def relu_active_sets(self) -> Dict[Tuple[str, int], torch.Tensor]:
         """Diagnostics / parity tests: the ReLU active sets of the last ``forward(save_for_backward=True)``,
         {("backcast" | "forecast", layer): uint8 [pixels of the (padded) activation buffer, hidden]} -- what
         ``threshold_backward`` of feedforward.py:17 would see.  Split-bf16 feed-forward only."""
-        if self._saved is not None and self.general_ff:
-            _, B, S, _, _ = self._saved
-            ws = self._forward_workspace(B, S)
+        ws = self._saved_pass("relu_active_sets()").ws
+        if self.general_ff:
             # a LIST per block: one active set per hidden activation; with dropout a dropped unit counts as inactive
             return {(kind, l): [(h > 0).to(torch.uint8) for h in ws.HG[kind][l]] for kind in ws.HG for l in range(self.L)
                     if not (kind == "backcast" and self.use_fork and l == self.L - 1)}
-        if self._saved is None or not self._ffx():
+        if not self._ffx():
             raise RuntimeError("relu_active_sets() needs a preceding forward(save_for_backward=True) on the ffx path")
-        _, B, S, _, _ = self._saved
-        ws = self._forward_workspace(B, S)
         lib = _lib.get_lib()
         st = _lib.current_stream(self.device)
         out = {}
@@ -1698,10 +1700,7 @@ class FFNOEngine:
         """Diagnostics / parity tests: the dropout masks of the last training forward, regenerated from their seeds:
         {("backcast" | "forecast", layer): [keep mask (uint8 [pixels, features]) behind every linear of the block]} and
         {"in": keep mask of the lifted features} -- what nn.Dropout drew in the reference (feedforward.py:16, grid_2d.py:158)."""
-        if self._saved is None:
-            raise RuntimeError("dropout_keep_sets() needs a preceding forward(save_for_backward=True)")
-        _, B, S, _, _ = self._saved
-        ws = self._forward_workspace(B, S)
+        ws = self._saved_pass("dropout_keep_sets()").ws
         lib = _lib.get_lib()
         st = _lib.current_stream(self.device)
         out = {}

@@ -61,7 +61,7 @@ def test_train_steps_match_golden_under_every_backward_schedule(host_device, def
         assert abs(loss.item() - float(g["losses"][s])) < 2e-5 * max(1.0, float(g["losses"][s]))
     ws = eng._ws
     assert bool(getattr(ws, "defer_wgrad", False)) == deferred and (getattr(ws, "lazy_sums", "") or "0") == (lazy if deferred else "0")
-    assert bool(getattr(eng, "_saved_lazy", False)) == (deferred and lazy != "0")
+    assert eng._saved.plan.lazy == (deferred and lazy != "0")
     assert (ws.wg_jobs is not None and len(ws.wg_jobs) == kw["n_layers"]) == deferred
     named = dict(blk.named_parameters())
     for n in [k for k in gu.packed_names(g) if k.startswith("final.")]:
@@ -122,17 +122,17 @@ def test_backward_uses_the_workspace_its_forward_filled(host_device):
     x_np, t_np = gu.make_block_io(kw, seed + 1, B, M, N)
     x = torch.from_numpy(x_np).to(host_device)
     out = eng.forward(x, True)
-    ws = eng._saved_ws
+    ws = eng._saved.ws
     assert ws is eng._ws
     gy = torch.ones_like(out)
     ref = eng.backward(gy).clone()
     # a validation-sized forward in between moves the engine's current workspace; the saved one is still the forward's
     out = eng.forward(x, True)
-    ws = eng._saved_ws
+    ws = eng._saved.ws
     eng._workspace(1, (M, N), False)
     assert eng._ws is not ws
     again = eng.backward(gy)
-    assert eng._saved_ws is ws
+    assert eng._saved.ws is ws
     np.testing.assert_array_equal(again.cpu().numpy(), ref.cpu().numpy())
     # an arithmetic switch between the two passes: refused (it used to differentiate uninitialised memory)
     eng.forward(x, True)
@@ -143,15 +143,15 @@ def test_backward_uses_the_workspace_its_forward_filled(host_device):
     np.testing.assert_array_equal(eng.backward(gy).cpu().numpy(), ref.cpu().numpy())
 
 
-def test_deferred_launch_falls_back_beyond_its_memory_limit(host_device, monkeypatch):
+def test_deferred_launch_falls_back_beyond_its_memory_limit(host_device):
     """the all-layers weight-gradient launch keeps one gradient buffer per layer (and, with lazy sums, both branch
-    outputs of every layer).  Beyond FFNO_FF_DEFER_MAX_BYTES the engine keeps the ping-pong pair and per-layer launches -- same
+    outputs of every layer).  Beyond engine.ff_defer_max_bytes the engine keeps the ping-pong pair and per-layer launches -- same
     golden losses."""
-    monkeypatch.setenv("FFNO_FF_DEFER_MAX_BYTES", "1")
     g = gu.load_golden("train_c64_2l")
     kw = gu.golden_kwargs(g)
     B, M, N, seed, steps = [int(v) for v in g["meta"]]
     blk, tr = make_trainer(kw, seed, host_device)
+    tr.engine.ff_defer_max_bytes = 1
     for s in range(steps):
         x_np, t_np = gu.make_block_io(kw, seed + 1 + s, B, M, N)
         loss = tr.train_step(torch.from_numpy(x_np).to(host_device), torch.from_numpy(t_np).to(host_device))
