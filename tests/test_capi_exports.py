@@ -27,6 +27,28 @@ def test_library_exports_every_declared_symbol():
     assert lib.ffno_abi_version() == int(m.group(1)) == _capi.ABI_VERSION
 
 
+# Declared functions that no tests/test_*.py has to name, each with its reason.  Nothing that launches a kernel belongs here: an
+# entry point that does is pinned by a kernel-level test calling it through the C ABI.
+UNNAMED_ON_PURPOSE = {
+    "ffno_abi_version": "host-only constant; asserted above against the header and the ctypes table",
+    "ffno_build_target": "host-only constant; asserted above and by backend_util.emu_lib for the emulator build",
+    "ffno_twiddle_fill_host": "host-only table fill; checked by test_host_twiddle_table below, called by backend_util.Backend.twiddle",
+}
+
+
+def test_every_declared_function_is_named_by_a_test():
+    """Every function of include/ffno.h appears by name in at least one test module other than this one, so a new entry point
+    cannot go in without a test that calls it."""
+    import glob
+    tests_dir = os.path.join(ROOT, "tests")
+    texts = [open(f).read() for f in sorted(glob.glob(os.path.join(tests_dir, "test_*.py")))
+             if os.path.basename(f) != os.path.basename(__file__)]
+    declared = header_functions()
+    assert set(UNNAMED_ON_PURPOSE) <= declared, set(UNNAMED_ON_PURPOSE) - declared
+    unnamed = {fn for fn in declared if not any(re.search(r"\b%s\b" % fn, t) for t in texts)}
+    assert unnamed == set(UNNAMED_ON_PURPOSE), (sorted(unnamed - set(UNNAMED_ON_PURPOSE)), sorted(set(UNNAMED_ON_PURPOSE) - unnamed))
+
+
 def test_loader_refuses_a_library_of_another_abi_generation():
     import pytest
     from fourierflow_amd import _capi, _lib

@@ -1,5 +1,9 @@
 """Feed-forward / pointwise kernels through the C ABI vs fp64 numpy references -- on the CPU wave
-emulator (-m "not gpu") and on the MI355X (-m gpu)."""
+emulator (-m "not gpu") and on the MI355X (-m gpu).
+
+Worst measured rel-L2 against fp64 of the lift gradient groups (band: TOL = 1e-5, the kernel tolerance of these files):
+    ffno_lift_bwd_data   emulator 1.5e-7   MI355X 1.5e-7 (1.4e-7 at P = 300 000, the grid-stride second pass)
+    ffno_lift_bwd2       emulator 1.9e-7   MI355X 1.9e-7; bit-identical to ffno_lift_bwd on the pre-summed image on both"""
 import ctypes
 
 import numpy as np
@@ -286,3 +290,115 @@ def test_adamw_and_axpy(be):
     dy, dxv = be.put(yv), be.put(xv)
     assert lib.ffno_axpy(p(dy), p(dxv), 0.5, 100, None) == 0
     np.testing.assert_allclose(be.get(dy), yv + 0.5 * xv, rtol=1e-6)
+
+
+# ---- the lift's data gradient and its two-buffer parameter gradient ----------------------------------------------------------
+LIFT_PAD = (2, (3, 7, 5), (5, 9, 6))            # B, unpadded and padded sizes of the 3-D mesh path
+LIFT_SHAPES = [(64, 4), (32, 63), (32, 1)]      # (C, Cin): both widths, Cin at its limit of 63 and at 1
+
+
+def _padded_gradient(rs, Bn, size, padded, C):
+    """-> (q, g[Pp][C]): a gradient image in the padded buffer whose PAD region holds large random values -- nothing of it may
+    reach a result."""
+    Pp = Bn * int(np.prod(padded))
+    q = pad_index(Bn, size, padded)
+    g = rs.standard_normal((Pp, C)).astype(np.float32)
+    in_pad = np.ones(Pp, bool)
+    in_pad[q] = False
+    g[in_pad] *= 1e3
+    return q, g
+
+
+def _lift_bwd_data_case(be, P, Cin, C, g, q, pm):
+    rs = np.random.RandomState(P + Cin + C)
+    W = rs.standard_normal((C, Cin)).astype(np.float32)
+    dx = be.empty((P, Cin))
+    assert be.lib.ffno_lift_bwd_data(be.ptr(be.put(g)), be.ptr(be.put(W)), be.ptr(dx), P, Cin, C,
+                                     ctypes.byref(pm) if pm is not None else None, None) == 0
+    gq = g if q is None else g[q]
+    err = rel_l2(be.get(dx), gq.astype(np.float64) @ W.astype(np.float64))
+    print(f"lift_bwd_data {be.kind} P={P} Cin={Cin} C={C} pad={pm is not None}: rel-L2 {err:.3g}")
+    return err
+
+
+@pytest.mark.parametrize("C,Cin", LIFT_SHAPES)
+def test_lift_bwd_data_through_pad_map(be, C, Cin):
+    """dx[p] = gout[q(p)] @ W with q the pad map of the 3-D mesh operator."""
+    Bn, size, padded = LIFT_PAD
+    P = Bn * int(np.prod(size))
+    q, g = _padded_gradient(np.random.RandomState(C + Cin), Bn, size, padded, C)
+    assert _lift_bwd_data_case(be, P, Cin, C, g, q, padmap(be, size, padded)) < TOL
+
+
+@pytest.mark.parametrize("C,Cin", LIFT_SHAPES)
+def test_lift_bwd_data_without_pad_map(be, C, Cin):
+    P = 333                                      # two workgroups, the second one ragged
+    g = np.random.RandomState(C + Cin).standard_normal((P, C)).astype(np.float32)
+    assert _lift_bwd_data_case(be, P, Cin, C, g, None, None) < TOL
+    # a pad map that pads nothing is the identity
+    assert _lift_bwd_data_case(be, P, Cin, C, g, None, padmap(be, (1, 9, 37), (1, 9, 37))) < TOL
+
+
+def test_lift_bwd_data_grid_stride_second_pass(be):
+    """More pixels than one pass of the launch covers (256 threads x 4 workgroups x 256 compute units = 262 144)."""
+    if be.kind == "emu":
+        pytest.skip("large case runs on the GPU only")
+    P, Cin, C = 300000, 3, 64
+    g = np.random.RandomState(1).standard_normal((P, C)).astype(np.float32)
+    assert _lift_bwd_data_case(be, P, Cin, C, g, None, None) < TOL
+
+
+def test_lift_bwd_data_refusals(be):
+    """Every one of these is rejected by the argument checks, before anything is launched."""
+    z, p, f = be.zeros(64 * 64), be.ptr, be.lib.ffno_lift_bwd_data
+    assert f(None, p(z), p(z), 4, 3, 64, None, None) == -1
+    assert f(p(z), None, p(z), 4, 3, 64, None, None) == -1
+    assert f(p(z), p(z), None, 4, 3, 64, None, None) == -1
+    assert f(p(z), p(z), p(z), 0, 3, 64, None, None) == -1
+    assert f(p(z), p(z), p(z), -5, 3, 64, None, None) == -1
+    assert f(p(z), p(z), p(z), 4, 64, 64, None, None) == -2      # Cin <= 63
+    assert f(p(z), p(z), p(z), 4, 3, 48, None, None) == -2       # widths 32 and 64 only
+
+
+@pytest.mark.parametrize("C,Cin", LIFT_SHAPES)
+def test_lift_bwd2_adds_the_second_gradient_image(be, C, Cin):
+    """ffno_lift_bwd2: the parameter gradients of gout + gout2, summed while the rows are staged -- through the pad map, against
+    fp64 and BIT FOR BIT against ffno_lift_bwd on the pre-summed image (the engine picks either path)."""
+    lib, p = be.lib, be.ptr
+    Bn, size, padded = LIFT_PAD
+    P, nsplit = Bn * int(np.prod(size)), 3
+    rs = np.random.RandomState(C * Cin)
+    q, g = _padded_gradient(rs, Bn, size, padded, C)
+    _, g2 = _padded_gradient(rs, Bn, size, padded, C)
+    x = rs.standard_normal((P, Cin)).astype(np.float32)
+    pm = ctypes.byref(padmap(be, size, padded))
+    dx_, dg, dg2, dgs = be.put(x), be.put(g), be.put(g2), be.put(g + g2)       # (g + g2: one fp32 addition, as the kernel's)
+
+    def run(fn, *gs, acc=0, start=None):
+        part = be.empty(nsplit * C * (Cin + 1))
+        gW = be.empty((C, Cin)) if start is None else be.put(start[0])
+        gb = be.empty(C) if start is None else be.put(start[1])
+        assert fn(p(dx_), *gs, p(part), p(gW), p(gb), P, Cin, C, nsplit, acc, pm, None) == 0
+        return np.array(be.get(gW)).copy(), np.array(be.get(gb)).copy()
+
+    gs64 = (g.astype(np.float64) + g2)[q]
+    refW, refb = gs64.T @ x.astype(np.float64), gs64.sum(0)
+    gW, gb = run(lib.ffno_lift_bwd2, p(dg), p(dg2))
+    errs = [rel_l2(gW, refW), rel_l2(gb, refb)]
+    oW, ob = run(lib.ffno_lift_bwd, p(dgs))
+    np.testing.assert_array_equal(gW, oW)
+    np.testing.assert_array_equal(gb, ob)
+    # no second image: the one-image entry point
+    nW, nb = run(lib.ffno_lift_bwd2, p(dg), None)
+    oW1, ob1 = run(lib.ffno_lift_bwd, p(dg))
+    np.testing.assert_array_equal(nW, oW1)
+    np.testing.assert_array_equal(nb, ob1)
+    errs += [rel_l2(nW, g[q].astype(np.float64).T @ x), rel_l2(nb, g[q].astype(np.float64).sum(0))]
+    # accumulate: one fp32 addition onto what the buffers hold
+    start = rs.standard_normal((C, Cin)).astype(np.float32), rs.standard_normal(C).astype(np.float32)
+    aW, ab = run(lib.ffno_lift_bwd2, p(dg), p(dg2), acc=1, start=start)
+    errs += [rel_l2(aW, start[0] + refW), rel_l2(ab, start[1] + refb)]
+    np.testing.assert_array_equal(aW, start[0] + gW)
+    np.testing.assert_array_equal(ab, start[1] + gb)
+    print(f"lift_bwd2 {be.kind} C={C} Cin={Cin}: rel-L2 {max(errs):.3g}")
+    assert max(errs) < TOL

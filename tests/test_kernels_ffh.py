@@ -1,6 +1,9 @@
 """fp16x2 feed-forward kernels (ffno_ffh_*, fourierflow_amd/csrc/ffx.hip with the SplitHf2 policy) through the C ABI vs fp64
 numpy references -- on the CPU wave emulator (-m "not gpu") and on the MI355X (-m gpu).  Same operator, masks and tolerance as
-the bf16x3 family (test_kernels_ffx.py); what differs is the operand format, so the range behaviour is tested as well."""
+the bf16x3 family (test_kernels_ffx.py); what differs is the operand format, so the range behaviour is tested as well.
+
+The sign words of ffno_ffh_fwd2 (default schedule and FFNO_FF_SCHED_IN_PHASE) decoded by ffno_ffx_mask_unpack: no mismatch with the
+fp64 pre-activations on the emulator or on the MI355X, inside or outside the undecided band (figures: test_kernels_ffx.py)."""
 import ctypes
 
 import numpy as np
@@ -9,6 +12,7 @@ import pytest
 from backend_util import be, rel_l2  # noqa: F401
 from fourierflow_amd._capi import FfOpts, FxPackDesc
 from test_kernels_ff import ff_ref
+from test_kernels_ffx import MASK_SHAPES, check_mask_unpack, mask_case_inputs, random_mask_words
 
 FFNO_FF_SCHED_IN_PHASE = 1
 
@@ -174,6 +178,23 @@ def test_ffh_fwd_bwd(be, P, C, H, sched):
     # without a range word the same call still works, only less accurately (documented: gradual below 6e-5)
     assert lib.ffno_ffh_bwd_data2(p(be.put(db)), None, None, p(mask), p(a1b), p(a2b), p(ds), P, C, H, None, None) == 0
     assert rel_l2(be.get(ds), ref_ds) < 3e-5
+
+
+@pytest.mark.parametrize("sched", [0, FFNO_FF_SCHED_IN_PHASE], ids=["default", "in_phase"])
+@pytest.mark.parametrize("P,C,H", MASK_SHAPES)
+def test_ffh_masks_unpack_to_the_preactivations(be, P, C, H, sched):
+    """The sign words the fp16x2 forward leaves (default schedule and FFNO_FF_SCHED_IN_PHASE), decoded by ffno_ffx_mask_unpack,
+    against the fp64 pre-activations (test_kernels_ffx.check_mask_unpack)."""
+    if be.kind == "emu" and P > 1000:
+        pytest.skip("large case runs on the GPU only")
+    lib, p = be.lib, be.ptr
+    s, resid, W1, b1, W2, b2 = mask_case_inputs(P, C, H)
+    (a1, a2, _a1b, _a2b), _keep = pack_weights_h(be, W1, W2)
+    out, mask = be.empty((P, C)), random_mask_words(be, P, H)
+    o = opts(be, amax_word(be, s), schedule=sched)
+    assert lib.ffno_ffh_fwd2(p(be.put(s)), None, None, p(be.put(resid)), p(a1), p(be.put(b1)), p(a2), p(be.put(b2)), p(out), p(mask),
+                             P, C, H, ctypes.byref(o), None) == 0
+    check_mask_unpack(be, mask, P, C, H, s, W1, b1, "ffh_fwd2 schedule %d" % sched)
 
 
 FFNO_FF_SCHED_WAVE_TILES, FFNO_FF_SCHED_ROLE_SPLIT = 2, 3

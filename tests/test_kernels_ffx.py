@@ -1,13 +1,20 @@
 """bf16x3 feed-forward kernels (fourierflow_amd/csrc/ffx.hip) through the C ABI vs fp64 numpy references -- on the CPU
 wave emulator (-m "not gpu") and on the MI355X (-m gpu).  Same operator and the same tolerance as the fp32-MFMA kernels
-of test_kernels_ff.py: the split arithmetic must be fp32-grade."""
+of test_kernels_ff.py: the split arithmetic must be fp32-grade.
+
+Worst measured figures of the reduce / mask-decoding groups (band: TOL = 1e-5):
+    ffno_ffx_bwd_weights_reduce_batched   rel-L2 vs fp64: emulator 9.6e-8, MI355X 9.6e-8; bit-identical to the one-block reduce
+    ffno_ffx_mask_unpack (ffno_ffx_fwd masks here, ffno_ffh_fwd2 masks in test_kernels_ffh.py): share of (pixel, hidden unit) pairs
+        whose fp64 pre-activation is too close to zero to decide: at most 4.0e-5 (bound asserted: 1e-3); mismatches among the
+        decided ones: 0 required; mismatches among the undecided ones: 0 observed on the emulator and on the MI355X, P = 5000
+        included"""
 import ctypes
 
 import numpy as np
 import pytest
 
 from backend_util import be, rel_l2  # noqa: F401
-from fourierflow_amd._capi import FfOpts, FxPackDesc
+from fourierflow_amd._capi import FfOpts, FxPackDesc, FxRedDesc
 from test_kernels_ff import ff_ref
 
 TOL = 1e-5
@@ -203,3 +210,103 @@ def test_ffx_chain_schedules_are_bit_identical(be, P, C, H, wgs):
     assert rel_l2(res[0][1], ref_out) < TOL
     # the bf16x3 family needs no range word but records its output maximum like the fp16x2 one (mixed configurations)
     assert res[0][5].view(np.float32)[0] == np.abs(res[0][1]).max()
+
+
+@pytest.mark.parametrize("C,H,nsplit,n", [(64, 256, 37, 3), (32, 128, 4, 2), (32, 64, 33, 1), (64, 128, 64, 2)])
+def test_ffx_bwd_weights_reduce_batched(be, C, H, nsplit, n):
+    """The table-driven reduction of n feed-forward blocks in one launch: slices {dW1^T[C][H], dW2[C][H], db1[H], db2[C]} summed
+    into dW1[H][C] (transposed), dW2, db1, db2 -- the 32-slice unrolled loop, its tail and nsplit < 32 -- against fp64 and bit for
+    bit against ffno_ffx_bwd_weights_reduce on the same slices (same summation order)."""
+    lib, p = be.lib, be.ptr
+    part = 2 * H * C + H + C
+    assert lib.ffno_ff_wgrad_partial_floats(C, H, nsplit) == nsplit * part
+    rs = np.random.RandomState(C + H + nsplit + n)
+    parts = [rs.standard_normal((nsplit, part)).astype(np.float32) for _ in range(n)]
+    dparts = [be.put(a) for a in parts]
+    outs = [(be.empty((H, C)), be.empty((C, H)), be.empty(H), be.empty(C)) for _ in range(n)]
+    descs = (FxRedDesc * n)(*[FxRedDesc(p(a), *[p(t) for t in o]) for a, o in zip(dparts, outs)])
+    table = be.put(np.frombuffer(bytes(descs), dtype=np.uint8))
+    assert lib.ffno_ffx_bwd_weights_reduce_batched(p(table), n, C, H, nsplit, None) == 0
+    worst = 0.0
+    for a, da, o in zip(parts, dparts, outs):
+        tot = a.astype(np.float64).sum(0)
+        ref = (tot[:H * C].reshape(C, H).T, tot[H * C:2 * H * C].reshape(C, H), tot[2 * H * C:2 * H * C + H], tot[2 * H * C + H:])
+        single = (be.empty((H, C)), be.empty((C, H)), be.empty(H), be.empty(C))
+        assert lib.ffno_ffx_bwd_weights_reduce(p(da), *[p(t) for t in single], C, H, nsplit, 0, None) == 0
+        for got, r, one in zip(o, ref, single):
+            worst = max(worst, rel_l2(be.get(got), r))
+            np.testing.assert_array_equal(be.get(got), be.get(one))
+    print(f"ffx_bwd_weights_reduce_batched {be.kind} C={C} H={H} nsplit={nsplit} n={n}: rel-L2 {worst:.3g}")
+    assert worst < TOL
+    assert lib.ffno_ffx_bwd_weights_reduce_batched(None, n, C, H, nsplit, None) == -1
+    assert lib.ffno_ffx_bwd_weights_reduce_batched(p(table), 0, C, H, nsplit, None) == -1
+    assert lib.ffno_ffx_bwd_weights_reduce_batched(p(table), n, C, H, 0, None) == -1
+
+
+# ---- ffno_ffx_mask_unpack: the instrument of every gradient parity test ("same ReLU active sets") -----------------------------
+MASK_SHAPES = [(70, 64, 256), (33, 32, 128), (64, 64, 128), (40, 32, 64), (97, 64, 256), (5000, 64, 256)]
+
+
+def mask_case_inputs(P, C, H):
+    """The operands of test_ffx_fwd_bwd (same generator, same order of draws)."""
+    rs = np.random.RandomState(P + C + H)
+    s = rs.standard_normal((P, C)).astype(np.float32)
+    resid = rs.standard_normal((P, C)).astype(np.float32)
+    W1 = (rs.standard_normal((H, C)) / np.sqrt(C)).astype(np.float32)
+    b1 = (rs.standard_normal(H) * 0.1).astype(np.float32)
+    W2 = (rs.standard_normal((C, H)) / np.sqrt(H)).astype(np.float32)
+    b2 = (rs.standard_normal(C) * 0.1).astype(np.float32)
+    return s, resid, W1, b1, W2, b2
+
+
+def decided_preactivations(s, W1, b1):
+    """-> (pre > 0, decided): the fp64 pre-activations pre = s W1^T + b1 and where their sign is beyond fp32-grade rounding of the
+    kernel's own sum, |pre| > 1e-5 (|s| |W1^T| + |b1|).  The undecided share must be small for the check to mean something; that is
+    asserted here, on the reference alone."""
+    s64, W64, b64 = s.astype(np.float64), W1.astype(np.float64), b1.astype(np.float64)
+    pre = s64 @ W64.T + b64
+    decided = np.abs(pre) > 1e-5 * (np.abs(s64) @ np.abs(W64).T + np.abs(b64))
+    share = 1.0 - decided.mean()
+    assert share < 1e-3, share
+    return pre > 0, decided, share
+
+
+def check_mask_unpack(be, mask, P, C, H, s, W1, b1, tag):
+    """Unpack `mask` (written by a forward over s, W1, b1) and compare it with the pre-activations."""
+    active_ref, decided, share = decided_preactivations(s, W1, b1)
+    active = be.put(np.full((P, H), 7, np.uint8))
+    assert be.lib.ffno_ffx_mask_unpack(be.ptr(mask), be.ptr(active), P, C, H, None) == 0
+    got = np.asarray(be.get(active))
+    assert np.isin(got, (0, 1)).all(), np.unique(got)
+    wrong = (got != active_ref) & decided
+    inside = int(((got != active_ref) & ~decided).sum())
+    print(f"ffx_mask_unpack {be.kind} {tag} P={P} C={C} H={H}: undecided share {share:.3g}, mismatches inside the band {inside}")
+    assert not wrong.any(), (int(wrong.sum()), np.argwhere(wrong)[:8])
+
+
+def random_mask_words(be, P, H):
+    """A mask buffer holding random bits, so a word the forward does not write shows."""
+    n = be.lib.ffno_ff_mask_words(P, H)
+    return be.put(np.random.RandomState(P + H).randint(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32))
+
+
+@pytest.mark.parametrize("P,C,H", MASK_SHAPES)
+def test_ffx_mask_unpack_matches_the_preactivations(be, P, C, H):
+    if be.kind == "emu" and P > 1000:
+        pytest.skip("large case (the grid-stride loop of the fixed 256 x 256 launch) runs on the GPU only")
+    lib, p = be.lib, be.ptr
+    s, resid, W1, b1, W2, b2 = mask_case_inputs(P, C, H)
+    (a1, a2, _a1b, _a2b), _keep = pack_weights(be, W1, W2)
+    out, mask = be.empty((P, C)), random_mask_words(be, P, H)
+    assert lib.ffno_ffx_fwd(p(be.put(s)), p(be.put(resid)), p(a1), p(be.put(b1)), p(a2), p(be.put(b2)), p(out), p(mask),
+                            P, C, H, None) == 0
+    check_mask_unpack(be, mask, P, C, H, s, W1, b1, "ffx_fwd")
+
+
+def test_ffx_mask_unpack_refusals(be):
+    """Rejected by the argument checks, before anything is launched."""
+    z, p = be.zeros(64), be.ptr
+    assert be.lib.ffno_ffx_mask_unpack(p(z), p(z), 1, 64, 64, None) == -2
+    assert be.lib.ffno_ffx_mask_unpack(None, p(z), 1, 64, 256, None) == -1
+    assert be.lib.ffno_ffx_mask_unpack(p(z), None, 1, 64, 256, None) == -1
+    assert be.lib.ffno_ffx_mask_unpack(p(z), p(z), 0, 64, 256, None) == -1

@@ -51,6 +51,7 @@ def test_glin_fwd_bwd(be, P, Cin, Cout, p_drop):
         yb = y if relu else None
         assert lib.ffno_glin_bwd_data(p(dg), p(yb), p(dW_), p(dx), P, Cin, Cout, p_drop, seed, 1, None) == 0      # accumulate onto ones
         assert rel_l2(be.get(dx), dpre @ W.astype(np.float64) + 1.0) < TOL
+        assert lib.ffno_glin_wgrad_partial_floats(P, Cin, Cout) == lib.ffno_glin_wgrad_nsplit(P) * (Cin * Cout + Cout)      # slice: {dW, db}
         part = be.zeros(lib.ffno_glin_wgrad_partial_floats(P, Cin, Cout))
         gW, gb = be.zeros((Cout, Cin)), be.zeros(Cout)
         for acc in (0, 1):

@@ -94,6 +94,7 @@ def test_plin_backward(be, P, Cin, ldx, Cout, ldo, masked):
             np.testing.assert_array_equal(got_dp[:, :Cout], dpre.astype(np.float32))
         assert not got_dp[:, Cout:].any()
 
+    assert be.lib.ffno_plin_wgrad_partial_floats(P, Cin, Cout) == be.lib.ffno_plin_wgrad_nsplit(P) * Cout * (Cin + 1)      # slice: {dW, db}
     part = be.empty(int(be.lib.ffno_plin_wgrad_partial_floats(P, Cin, Cout)))
     dW0 = rs.standard_normal((Cout, Cin)).astype(np.float32)
     db0 = rs.standard_normal(Cout).astype(np.float32)

@@ -1,5 +1,10 @@
 """Spectral kernels through the C ABI vs fp64 torch.fft / einsum references and the reference's golden
-vectors -- on the CPU wave emulator (-m "not gpu") and on the MI355X (-m gpu)."""
+vectors -- on the CPU wave emulator (-m "not gpu") and on the MI355X (-m gpu).
+
+Worst measured rel-L2 against fp64 of the n-tensor launches (band: TOL):
+    ffno_fw_grad_partial_multi + ffno_fw_grad_reduce_multi   emulator 1.8e-7   MI355X 1.1e-7 (the emulator sums an MFMA's products
+        in another order); slices bit-identical to single-problem ffno_fw_grad_partial launches on both
+    ffno_fw_pack_batched                                      exact (bit-identical to the single-tensor packs' transposes)"""
 import ctypes
 
 import numpy as np
@@ -1141,3 +1146,87 @@ def test_spectral_x3_staged_pair(be, B, M, N, K, direction):
         assert rel_l2(be.get(sv[i]), refs[i][1]) < TOL
     assert lib.ffno_spectral_x3_staged_pair(ctypes.byref(args[0]), ctypes.byref(args[0]), p(mixes[0]), p(mixes[1]), C, 0, 1, 0, None) == -1
     assert lib.ffno_spectral_x3_staged_supported(64, 33, 128) == 0 and lib.ffno_spectral_x3_staged_supported(32, 8, 64) == 0
+
+
+# ---- one-launch variants for n weight tensors: ffno_fw_pack_batched, ffno_fw_grad_partial_multi, ffno_fw_grad_reduce_multi ----
+def _addr(be, h, float_offset=0):
+    """Device address of element `float_offset` of the fp32 buffer h."""
+    return be.ptr(h).value + 4 * float_offset
+
+
+@pytest.mark.parametrize("C,Ks,reals", [(32, [16, 3, 8, 5], [0, 0, 1, 1]), (64, [2, 5], [1, 0])])
+def test_fw_pack_batched(be, C, Ks, reals):
+    """Complex [I][O][K][2] and real [I][O][K] weights with different K in one launch (max_K sizes the grid): every tensor's planes
+    are the transposes the single-tensor packs produce (test_mode_mix, test_kernels_dct.py), bit for bit, and a tensor with
+    K < max_K writes nothing outside its K*2*C*C floats."""
+    from fourierflow_amd._capi import FwPackDesc
+    lib, p = be.lib, be.ptr
+    rs = np.random.RandomState(C + len(Ks))
+    G = 3 * C * C + 8                                   # guard floats on either side of every output
+    ws = [rs.standard_normal((C, C, K) if real else (C, C, K, 2)).astype(np.float32) for K, real in zip(Ks, reals)]
+    dws = [be.put(w) for w in ws]
+    wps = [be.empty(2 * G + K * 2 * C * C) for K in Ks]
+    wpts = [be.empty(2 * G + K * 2 * C * C) for K in Ks]
+    descs = (FwPackDesc * len(Ks))(*[FwPackDesc(p(dw), _addr(be, a, G), _addr(be, b, G), K, real)
+                                     for dw, a, b, K, real in zip(dws, wps, wpts, Ks, reals)])
+    table = be.put(np.frombuffer(bytes(descs), dtype=np.uint8))
+    assert lib.ffno_fw_pack_batched(p(table), len(Ks), C, max(Ks), None) == 0
+    for w, a, b, K, real in zip(ws, wps, wpts, Ks, reals):
+        n = K * 2 * C * C
+        a, b = np.asarray(be.get(a)), np.asarray(be.get(b))
+        for buf in (a, b):
+            assert np.isnan(buf[:G]).all() and np.isnan(buf[G + n:]).all(), (K, real)
+        if real:
+            ref = np.stack([w.transpose(2, 0, 1), np.zeros((K, C, C), np.float32)], axis=1)      # [k][re|im][i][o]
+        else:
+            ref = w.transpose(2, 3, 0, 1)
+        np.testing.assert_array_equal(a[G:G + n].reshape(K, 2, C, C), ref)
+        np.testing.assert_array_equal(b[G:G + n].reshape(K, 2, C, C), ref.transpose(0, 1, 3, 2))
+    assert lib.ffno_fw_pack_batched(None, len(Ks), C, max(Ks), None) == -1
+    assert lib.ffno_fw_pack_batched(p(table), 0, C, max(Ks), None) == -1
+    assert lib.ffno_fw_pack_batched(p(table), len(Ks), C, 0, None) == -1
+
+
+@pytest.mark.parametrize("R,C,K,n,nsplit", [(37, 64, 2, 3, 3), (70, 32, 3, 2, 4), (48, 64, 1, 4, 2), (16, 32, 2, 3, 5)])
+def test_fw_grad_multi_partial_and_reduce(be, R, C, K, n, nsplit):
+    """The per-layer Fourier-weight gradient of an unshared model on the bf16x3 kernels: ffno_fw_grad_partial_multi (aligned and
+    ragged line counts at both widths, operand and slice strides larger than the payload) and ffno_fw_grad_reduce_multi (device
+    pointer table, complex / real outputs, overwrite / accumulate) against the fp64 contraction; the slices are bit for bit those
+    of n single-problem ffno_fw_grad_partial launches."""
+    lib, p = be.lib, be.ptr
+    rs = np.random.RandomState(R + C + K + n)
+    pay, ppay = K * R * 2 * C, nsplit * 2 * K * C * C
+    stride_x, stride_dy, stride_p = pay + 3 * 2 * C, pay + 7 * 2 * C + 4, ppay + 2 * C + 4
+    xs = rs.standard_normal((n, stride_x)).astype(np.float32)      # (the tails: random values nothing may read into a result)
+    dys = rs.standard_normal((n, stride_dy)).astype(np.float32)
+    dxs, ddys, partial = be.put(xs), be.put(dys), be.empty((n, stride_p))
+    assert lib.ffno_fw_grad_partial_multi(p(dxs), p(ddys), p(partial), R, C, K, nsplit, n, stride_x, stride_dy, stride_p, None) == 0
+    part = np.array(be.get(partial)).copy()
+    assert np.isnan(part[:, ppay:]).all() and not np.isnan(part[:, :ppay]).any()
+    refs = []
+    for z in range(n):
+        x4 = xs[z, :pay].reshape(K, R, 2, C).astype(np.float64)
+        d4 = dys[z, :pay].reshape(K, R, 2, C).astype(np.float64)
+        refs.append(np.einsum("kri,kro->iok", np.conj(x4[:, :, 0] + 1j * x4[:, :, 1]), d4[:, :, 0] + 1j * d4[:, :, 1]))
+        single = be.empty(ppay)
+        assert lib.ffno_fw_grad_partial(_addr(be, dxs, z * stride_x), _addr(be, ddys, z * stride_dy), p(single), R, C, K, nsplit,
+                                        0, 1, 0, 0, None) == 0
+        np.testing.assert_array_equal(part[z, :ppay], be.get(single))
+    worst = 0.0
+    for real in (0, 1):
+        for accumulate in (0, 1):
+            shape = (C, C, K) if real else (C, C, K, 2)
+            starts = [rs.standard_normal(shape).astype(np.float32) for _ in range(n)]
+            gws = [be.put(st) if accumulate else be.empty(shape) for st in starts]
+            table = be.put(np.array([_addr(be, g) for g in gws], np.uint64).view(np.uint8))
+            assert lib.ffno_fw_grad_reduce_multi(p(partial), p(table), n, C, K, nsplit, stride_p, accumulate, real, None) == 0
+            for z in range(n):
+                ref = refs[z].real if real else np.stack([refs[z].real, refs[z].imag], axis=-1)
+                if accumulate:
+                    ref = ref + starts[z]
+                worst = max(worst, rel_l2(be.get(gws[z]), ref))
+    print(f"fw_grad_multi {be.kind} R={R} C={C} K={K} n={n} nsplit={nsplit}: rel-L2 {worst:.3g}")
+    assert worst < TOL
+    assert lib.ffno_fw_grad_partial_multi(None, p(ddys), p(partial), R, C, K, nsplit, n, stride_x, stride_dy, stride_p, None) == -1
+    assert lib.ffno_fw_grad_partial_multi(p(dxs), p(ddys), p(partial), R, 48, K, nsplit, n, stride_x, stride_dy, stride_p, None) == -2
+    assert lib.ffno_fw_grad_reduce_multi(p(partial), None, n, C, K, nsplit, stride_p, 0, 0, None) == -1
