@@ -2569,86 +2569,190 @@ static int x3_args(X3Args& a, const ffno_fused_branch* b, int C, int scale_ck_fw
     return FFNO_OK;
 }
 
+// ---- which kernel a fused launch runs ------------------------------------------------------------------------------------------
+// ffno_spectral_x3, ffno_spectral_x3_pair and ffno_spectral_x3_mix_pair fill ONE selection (x3_pick) and look it up in the list of
+// shipped instances of its kernel family; a new kernel variant is a new row of one list.
+enum X3Family {
+    X3_WIDTH32,      // spectral_x3c32: width 32, 16 lines per workgroup, two per wave side by side
+    X3_MANY,         // spectral_x3k: 17..64 modes, 4 lines per workgroup, spectrum tile of 64 / 128 rows
+    X3_LATENCY,      // spectral_x3s: <= 16 modes, 4 lines per workgroup with two waves per line (x3_latency_tiles)
+    X3_TILES         // spectral_x3: <= 16 modes, 8 or 16 lines per workgroup
+};
+
+struct X3Pick {
+    X3Family family;
+    bool pair;           // the paired kernel (the single launch is the pair rule with an empty second branch)
+    int tile;            // lines per workgroup; X3_MANY: rows of the spectrum tile (64 / 128), on 4 lines
+    bool h2;             // MIXH2 instances: the split-fp16 path (fp16x2 packs; every bf16-storage twin)
+    bool b16;            // bf16 storage
+    bool tab, m16, cs, mixout;
+    int n0, n1;          // workgroups of branch a / b
+    size_t smem;
+    int interleave;      // X3_TILES pair: the workgroup -> branch map (x3_wg_map) and ...
+    int skew;            // ... the start skew of every other workgroup, in cycles
+};
+
+constexpr unsigned x3_key(int tile, bool h2, bool b16, bool tab = false, bool m16 = false, bool cs = false, bool mixout = false) {
+    return (unsigned)tile | h2 << 8 | b16 << 9 | tab << 10 | m16 << 11 | cs << 12 | mixout << 13;
+}
+
+using X3Single = void (*)(X3Args);
+using X3Pair = void (*)(X3Args, X3Args, int, int);               // (a, b, n0, n1)
+using X3TilesPair = void (*)(X3Args, X3Args, int, int, int);     // (a, b, n0, interleave, skew)
+template <class PairFn>
+struct X3Row {
+    unsigned key;
+    X3Single single;      // nullptr: the instance ships for the pair only
+    PairFn pair;
+};
+
+// a row from the template arguments of its instance: the key cannot disagree with the kernel
+template <class ST>
+constexpr bool kIsBf16 = std::is_same<ST, StBf16>::value;
+template <bool MIXH2, class ST = StF32, bool TAB = false>
+constexpr X3Row<X3Pair> x3c32_row() {
+    return {x3_key(16, MIXH2, kIsBf16<ST>, TAB), spectral_x3c32_kernel<MIXH2, ST, TAB>, spectral_x3c32_pair_kernel<MIXH2, ST, TAB>};
+}
+template <int KKT, bool MIXH2, class ST = StF32, bool TAB = false, bool M16 = false>
+constexpr X3Row<X3Pair> x3k_row() {
+    return {x3_key(KKT, MIXH2, kIsBf16<ST>, TAB, M16), spectral_x3k_kernel<KKT, MIXH2, ST, TAB, M16>,
+            spectral_x3k_pair_kernel<KKT, MIXH2, ST, TAB, M16>};
+}
+template <bool MIXH2, bool TAB = false, bool CS = false>
+constexpr X3Row<X3Pair> x3s_row() {
+    return {x3_key(4, MIXH2, false, TAB, false, CS), spectral_x3s_kernel<MIXH2, TAB, CS>, spectral_x3s_pair_kernel<MIXH2, TAB, CS>};
+}
+// (the single launch ships neither a DFT-fragment-table nor a mixed-spectrum instance)
+template <int NL, bool MIXH2, class ST = StF32, bool MIXOUT = false, bool DFTTAB = false>
+constexpr X3Row<X3TilesPair> x3_row() {
+    X3Single single = nullptr;
+    if constexpr (!MIXOUT && !DFTTAB) single = spectral_x3_kernel<NL, MIXH2, ST>;
+    return {x3_key(NL, MIXH2, kIsBf16<ST>, DFTTAB, false, false, MIXOUT), single, spectral_x3_pair_kernel<NL, MIXH2, ST, MIXOUT, DFTTAB>};
+}
+
+// the row of a selection whose kernel for this kind of launch (single / pair) ships, or nullptr
+template <class Row, size_t N>
+static const Row* x3_find(const Row (&rows)[N], const X3Pick& p) {
+    const unsigned key = x3_key(p.tile, p.h2, p.b16, p.tab, p.m16, p.cs, p.mixout);
+    for (const Row& r : rows)
+        if (r.key == key && (p.pair ? r.pair != nullptr : r.single != nullptr)) return &r;
+    return nullptr;
+}
+
+// ---- the shipped instances, one list per kernel family ---------------------------------------------------------------------------
+static constexpr X3Row<X3Pair> kX3c32Rows[] = {
+    x3c32_row<true, StBf16, true>(), x3c32_row<true, StBf16>(), x3c32_row<true, StF32, true>(), x3c32_row<true>(), x3c32_row<false>()};
+static constexpr X3Row<X3Pair> kX3kRows[] = {
+    x3k_row<64, true, StBf16, true, true>(),  x3k_row<64, true, StF32, true, true>(),  x3k_row<64, true, StBf16, true>(),
+    x3k_row<64, true, StBf16>(),              x3k_row<64, true, StF32, true>(),        x3k_row<64, true>(),
+    x3k_row<64, false>(),
+    x3k_row<128, true, StBf16, true, true>(), x3k_row<128, true, StF32, true, true>(), x3k_row<128, true, StBf16, true>(),
+    x3k_row<128, true, StBf16>(),             x3k_row<128, true, StF32, true>(),       x3k_row<128, true>(),
+    x3k_row<128, false>()};
+static constexpr X3Row<X3Pair> kX3sRows[] = {
+    x3s_row<true, true, true>(), x3s_row<true, false, true>(), x3s_row<true, true>(), x3s_row<true>(), x3s_row<false>()};
+static constexpr X3Row<X3TilesPair> kX3Rows[] = {
+    x3_row<8, true, StBf16, false, true>(),  x3_row<8, true, StBf16>(),  x3_row<8, true, StF32, false, true>(),  x3_row<8, true>(),
+    x3_row<8, false>(),                      x3_row<8, true, StF32, true, true>(),  x3_row<8, true, StF32, true>(),
+    x3_row<16, true, StBf16, false, true>(), x3_row<16, true, StBf16>(), x3_row<16, true, StF32, false, true>(), x3_row<16, true>(),
+    x3_row<16, false>(),                     x3_row<16, true, StF32, true, true>(), x3_row<16, true, StF32, true>()};
+
+// workgroup -> branch map of the X3_TILES pair.  interleave: bit 0 = even / odd workgroups; bit 1 = image-local map where the shapes
+// allow it (else bit 0 decides)
+static int x3_wg_map(const ffno_fused_branch* ba, const ffno_fused_branch* bb, int interleave, int NL, int n0, int n1) {
+    if (n0 != n1) return 0;
+    const bool square = ba->B == bb->B && ba->M == bb->M && ba->N == bb->N && ba->M == ba->N && ba->axis != bb->axis;
+    if ((interleave & 2) && square && ba->B % 8 == 0 && ba->M % NL == 0) return 2 | ((ba->M / NL) << 8);
+    return (interleave & 1) ? 1 : 0;
+}
+
+// The selection of one launch from the validated arguments of its two branches (x3_args / mix_pair_args) and their descriptors; the
+// single launch passes its one branch twice, the second with R = 0.  interleave: x3_wg_map in bits 0 and 1, bits 8.. = start skew of
+// every other workgroup in units of 256 cycles.  Nulls both `dft` where the many-mode kernel cannot use the tables.
+static int x3_pick(X3Pick& p, X3Args& a, X3Args& b, const ffno_fused_branch* ba, const ffno_fused_branch* bb, int C, bool pair,
+                   int interleave, bool mixout) {
+    // both branches of a pair carry the same kind of planes (or none) and the same tile choice
+    if ((ba->planes == nullptr) != (bb->planes == nullptr) || ba->planes_format != bb->planes_format ||
+        ba->tile_lines != bb->tile_lines || ba->storage != bb->storage)
+        return FFNO_EINVAL;
+    const bool h2 = ba->planes && ba->planes_format != FFNO_PLANES_BF16X3;
+    const bool many = x3_many_modes(a.K) || x3_many_modes(b.K);      // 17..64 modes on either axis: both on the 4-line tile
+    p = X3Pick{};
+    p.pair = pair, p.mixout = mixout;
+    p.b16 = ba->storage == FFNO_STORE_BF16;      // (x3_args: only with fp16x2 packs outside the K <= 16 kernel, ...
+    p.h2 = h2 || p.b16;                          //  ... whose bf16 twins are MIXH2 instances with or without packs)
+    p.smem = sizeof(float) * 2 * max(a.L, b.L);
+    if (p.b16 && !h2 && (C != X3Cfg::C || many)) return FFNO_EUNSUPPORTED;
+    const bool tabs = a.dft && b.dft;            // (x3_args: only with fp16x2 packs)
+    int lines = 4;
+    if (C == X3Cfg32::C) {
+        p.family = X3_WIDTH32, p.tile = lines = 16, p.tab = tabs;
+    } else if (many) {
+        // the table kernel needs BOTH branches' tables, laid out for the launch's tile height (64 / 128 rows): a branch with
+        // <= 16 modes dragged onto this kernel, or <= 32 next to > 32, has none that fits -- then both build on the fly
+        p.family = X3_MANY, p.tile = max(a.K, b.K) <= 32 ? 64 : 128;
+        p.tab = tabs && x3_many_modes(a.K) && x3_many_modes(b.K) && (a.K <= 32 ? 64 : 128) == p.tile && (b.K <= 32 ? 64 : 128) == p.tile;
+        if (!p.tab) a.dft = b.dft = nullptr;
+        p.m16 = ba->planes && ba->planes_format == FFNO_PLANES_FP16X2_M16;
+        if (p.m16 && !p.tab) return FFNO_EUNSUPPORTED;      // (the 16-row mix ships with the table kernels only)
+    } else if (!mixout && x3_latency_tiles(a.R, b.R, ba->tile_lines, ba->storage)) {
+        p.family = X3_LATENCY, p.tile = 4, p.tab = tabs;
+        p.cs = x3_latency_split(a.R, b.R, ba->tile_lines, h2 && a.wpk && b.wpk);
+    } else {
+        // 8-line tiles when they still fit one round of workgroups (one per CU), else 16-line tiles.  Split-fp16 DFT with both
+        // branches' fragment tables (ffno_spectral_x3_dft_frags for the launch's direction): no wave rebuilds the DFT matrices from the
+        // twiddles (same values: results bit-identical with and without the tables)
+        p.family = X3_TILES, p.tile = lines = x3_small_tiles(a.R, b.R, ba->tile_lines) ? 8 : 16;
+        p.tab = h2 && a.wpk && b.wpk && tabs;
+        if (!pair && p.tab && !x3_find(kX3Rows, p)) p.tab = false;      // (the single launch rebuilds: no table instance in the list)
+    }
+    const int per_tile = p.cs ? 2 : 1;      // (the channel split: two workgroups per tile)
+    p.n0 = per_tile * ((a.R + lines - 1) / lines), p.n1 = per_tile * ((b.R + lines - 1) / lines);
+    if (p.family == X3_TILES) {
+        p.interleave = x3_wg_map(ba, bb, interleave, p.tile, p.n0, p.n1);
+        p.skew = mixout ? 0 : (interleave >> 8) * 256;
+    }
+    return FFNO_OK;
+}
+
+// one launch of a family: the dynamic-LDS opt-in (the many-mode kernels: beyond the default window), the launch, its status.
+// tail = what the pair kernel takes behind (a, b, n0)
+template <class PairFn, class... Tail>
+static int x3_launch(const X3Row<PairFn>* r, const X3Pick& p, const X3Args& a, const X3Args& b, hipStream_t st, Tail... tail) {
+    if (!r) return FFNO_EUNSUPPORTED;      // (a selection without a shipped instance)
+    if (p.family == X3_MANY) {
+        const int rc = p.pair ? allow_dynamic_lds(r->pair, p.smem) : allow_dynamic_lds(r->single, p.smem);
+        if (rc) return rc;
+    }
+    if (p.pair)
+        FFNO_LAUNCH(r->pair, dim3(p.n0 + p.n1), dim3(512), p.smem, st, a, b, p.n0, tail...);
+    else
+        FFNO_LAUNCH(r->single, dim3(p.n0), dim3(512), p.smem, st, a);
+    return x3_status();
+}
+
+static int x3_run(X3Args& a, X3Args& b, const ffno_fused_branch* ba, const ffno_fused_branch* bb, int C, bool pair, int interleave,
+                  bool mixout, void* stream) {
+    X3Pick p;
+    const int rc = x3_pick(p, a, b, ba, bb, C, pair, interleave, mixout);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    switch (p.family) {
+    case X3_WIDTH32: return x3_launch(x3_find(kX3c32Rows, p), p, a, b, st, p.n1);
+    case X3_MANY: return x3_launch(x3_find(kX3kRows, p), p, a, b, st, p.n1);
+    case X3_LATENCY: return x3_launch(x3_find(kX3sRows, p), p, a, b, st, p.n1);
+    default: return x3_launch(x3_find(kX3Rows, p), p, a, b, st, p.interleave, p.skew);
+    }
+}
+
 extern "C" int ffno_spectral_x3(const ffno_fused_branch* br, int C, int scale_ck_fwd, int apply_ck_inv, int conj_transpose,
                                 void* stream) {
     X3Args a;
     const int rc = x3_args(a, br, C, scale_ck_fwd, apply_ck_inv, conj_transpose);
     if (rc) return rc;
-    // 8-line tiles when they still fit one round of workgroups (one per CU), else 16-line tiles
-    const bool h2 = br->planes && br->planes_format != FFNO_PLANES_BF16X3;
-    const bool m16 = br->planes && br->planes_format == FFNO_PLANES_FP16X2_M16;      // (x3_args: many modes + table)
-    const size_t smem = sizeof(float) * 2 * a.L;
-    hipStream_t st = (hipStream_t)stream;
-    const bool b16 = br->storage == FFNO_STORE_BF16;      // (x3_args: only with fp16x2 packs outside the K <= 16 kernel)
-    if (C == X3Cfg32::C) {          // width 32: 16 lines per workgroup, two per wave side by side
-        const dim3 grid((a.R + 15) / 16);
-        if (b16 && a.dft)
-            FFNO_LAUNCH((spectral_x3c32_kernel<true, StBf16, true>), grid, dim3(512), smem, st, a);
-        else if (b16)
-            FFNO_LAUNCH((spectral_x3c32_kernel<true, StBf16>), grid, dim3(512), smem, st, a);
-        else if (h2 && a.dft)
-            FFNO_LAUNCH((spectral_x3c32_kernel<true, StF32, true>), grid, dim3(512), smem, st, a);
-        else if (h2)
-            FFNO_LAUNCH((spectral_x3c32_kernel<true>), grid, dim3(512), smem, st, a);
-        else
-            FFNO_LAUNCH((spectral_x3c32_kernel<false>), grid, dim3(512), smem, st, a);
-        return x3_status();
-    }
-    if (x3_many_modes(a.K)) {      // 17..64 modes: the 4-line tile
-        const dim3 grid((a.R + 3) / 4);
-#define X3K_LAUNCH(...)                                                                                  \
-    do {                                                                                                 \
-        const int rc_ = allow_dynamic_lds(spectral_x3k_kernel<__VA_ARGS__>, smem);                       \
-        if (rc_) return rc_;                                                                             \
-        FFNO_LAUNCH((spectral_x3k_kernel<__VA_ARGS__>), grid, dim3(512), smem, st, a);                   \
-    } while (0)
-        const bool tab = a.dft != nullptr;       // (x3_args: only with fp16x2 planes)
-        if (a.K <= 32) {
-            if (m16 && b16) X3K_LAUNCH(64, true, StBf16, true, true); else if (m16) X3K_LAUNCH(64, true, StF32, true, true);
-            else if (b16 && tab) X3K_LAUNCH(64, true, StBf16, true); else if (b16) X3K_LAUNCH(64, true, StBf16);
-            else if (h2 && tab) X3K_LAUNCH(64, true, StF32, true); else if (h2) X3K_LAUNCH(64, true); else X3K_LAUNCH(64, false);
-        } else {
-            if (m16 && b16) X3K_LAUNCH(128, true, StBf16, true, true); else if (m16) X3K_LAUNCH(128, true, StF32, true, true);
-            else if (b16 && tab) X3K_LAUNCH(128, true, StBf16, true); else if (b16) X3K_LAUNCH(128, true, StBf16);
-            else if (h2 && tab) X3K_LAUNCH(128, true, StF32, true); else if (h2) X3K_LAUNCH(128, true); else X3K_LAUNCH(128, false);
-        }
-#undef X3K_LAUNCH
-        return x3_status();
-    }
-    if (x3_latency_tiles(a.R, 0, br->tile_lines, br->storage)) {
-        const bool cs = x3_latency_split(a.R, 0, br->tile_lines, h2 && a.wpk);
-        const dim3 grid((cs ? 2 : 1) * ((a.R + 3) / 4));
-        if (cs && a.dft)
-            FFNO_LAUNCH((spectral_x3s_kernel<true, true, true>), grid, dim3(512), smem, st, a);
-        else if (cs)
-            FFNO_LAUNCH((spectral_x3s_kernel<true, false, true>), grid, dim3(512), smem, st, a);
-        else if (h2 && a.dft)
-            FFNO_LAUNCH((spectral_x3s_kernel<true, true>), grid, dim3(512), smem, st, a);
-        else if (h2)
-            FFNO_LAUNCH((spectral_x3s_kernel<true>), grid, dim3(512), smem, st, a);
-        else
-            FFNO_LAUNCH((spectral_x3s_kernel<false>), grid, dim3(512), smem, st, a);
-        return x3_status();
-    }
-    if (br->storage == FFNO_STORE_BF16) {
-        if (x3_small_tiles(a.R, 0, br->tile_lines))
-            FFNO_LAUNCH((spectral_x3_kernel<8, true, StBf16>), dim3((a.R + 7) / 8), dim3(512), smem, st, a);
-        else
-            FFNO_LAUNCH((spectral_x3_kernel<16, true, StBf16>), dim3((a.R + 15) / 16), dim3(512), smem, st, a);
-        return x3_status();
-    }
-    if (x3_small_tiles(a.R, 0, br->tile_lines)) {
-        if (h2)
-            FFNO_LAUNCH((spectral_x3_kernel<8, true>), dim3((a.R + 7) / 8), dim3(512), smem, st, a);
-        else
-            FFNO_LAUNCH((spectral_x3_kernel<8, false>), dim3((a.R + 7) / 8), dim3(512), smem, st, a);
-    } else {
-        if (h2)
-            FFNO_LAUNCH((spectral_x3_kernel<16, true>), dim3((a.R + 15) / 16), dim3(512), smem, st, a);
-        else
-            FFNO_LAUNCH((spectral_x3_kernel<16, false>), dim3((a.R + 15) / 16), dim3(512), smem, st, a);
-    }
-    return x3_status();
+    X3Args none = a;      // the pair rule with an empty second branch
+    none.R = 0;
+    return x3_run(a, none, br, br, C, false, 0, false, stream);
 }
 
 extern "C" int ffno_spectral_x3_pair(const ffno_fused_branch* ba, const ffno_fused_branch* bb, int C, int scale_ck_fwd,
@@ -2660,120 +2764,7 @@ extern "C" int ffno_spectral_x3_pair(const ffno_fused_branch* ba, const ffno_fus
     if (rc) return rc;
     rc = x3_args(b, bb, C, scale_ck_fwd, apply_ck_inv, conj_transpose);
     if (rc) return rc;
-    const size_t smem = sizeof(float) * 2 * max(a.L, b.L);
-    // both branches of a pair carry the same kind of planes (or none) and the same tile choice
-    if ((ba->planes == nullptr) != (bb->planes == nullptr) || ba->planes_format != bb->planes_format ||
-        ba->tile_lines != bb->tile_lines || ba->storage != bb->storage)
-        return FFNO_EINVAL;
-    const bool h2 = ba->planes && ba->planes_format != FFNO_PLANES_BF16X3;
-    const bool m16 = ba->planes && ba->planes_format == FFNO_PLANES_FP16X2_M16;
-    hipStream_t st = (hipStream_t)stream;
-    const bool b16 = ba->storage == FFNO_STORE_BF16;
-    if (b16 && !h2 && (C != X3Cfg::C || x3_many_modes(a.K) || x3_many_modes(b.K))) return FFNO_EUNSUPPORTED;
-    if (C == X3Cfg32::C) {
-        const int n0 = (a.R + 15) / 16, n1 = (b.R + 15) / 16;
-        const bool tab = a.dft && b.dft;
-        if (b16 && tab)
-            FFNO_LAUNCH((spectral_x3c32_pair_kernel<true, StBf16, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else if (b16)
-            FFNO_LAUNCH((spectral_x3c32_pair_kernel<true, StBf16>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else if (h2 && tab)
-            FFNO_LAUNCH((spectral_x3c32_pair_kernel<true, StF32, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else if (h2)
-            FFNO_LAUNCH((spectral_x3c32_pair_kernel<true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else
-            FFNO_LAUNCH((spectral_x3c32_pair_kernel<false>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        return x3_status();
-    }
-    if (x3_many_modes(a.K) || x3_many_modes(b.K)) {      // 17..64 modes on either axis: both on the 4-line tile
-        const int n0 = (a.R + 3) / 4, n1 = (b.R + 3) / 4;
-        const dim3 grid(n0 + n1);
-#define X3K_LAUNCH(...)                                                                                  \
-    do {                                                                                                 \
-        const int rc_ = allow_dynamic_lds(spectral_x3k_pair_kernel<__VA_ARGS__>, smem);                  \
-        if (rc_) return rc_;                                                                             \
-        FFNO_LAUNCH((spectral_x3k_pair_kernel<__VA_ARGS__>), grid, dim3(512), smem, st, a, b, n0, n1);   \
-    } while (0)
-        // the table kernel needs BOTH branches' tables, laid out for the launch's tile height (64 / 128 rows): a branch with
-        // <= 16 modes dragged onto this kernel, or <= 32 next to > 32, has none that fits -- then both build on the fly
-        const int kkt = max(a.K, b.K) <= 32 ? 64 : 128;
-        const bool tab = a.dft && b.dft && x3_many_modes(a.K) && x3_many_modes(b.K) && (a.K <= 32 ? 64 : 128) == kkt &&
-                         (b.K <= 32 ? 64 : 128) == kkt;
-        if (!tab) a.dft = b.dft = nullptr;
-        if (m16 && !tab) return FFNO_EUNSUPPORTED;      // (the 16-row mix ships with the table kernels only)
-        if (kkt == 64) {
-            if (m16 && b16) X3K_LAUNCH(64, true, StBf16, true, true); else if (m16) X3K_LAUNCH(64, true, StF32, true, true);
-            else if (b16 && tab) X3K_LAUNCH(64, true, StBf16, true); else if (b16) X3K_LAUNCH(64, true, StBf16);
-            else if (h2 && tab) X3K_LAUNCH(64, true, StF32, true); else if (h2) X3K_LAUNCH(64, true); else X3K_LAUNCH(64, false);
-        } else {
-            if (m16 && b16) X3K_LAUNCH(128, true, StBf16, true, true); else if (m16) X3K_LAUNCH(128, true, StF32, true, true);
-            else if (b16 && tab) X3K_LAUNCH(128, true, StBf16, true); else if (b16) X3K_LAUNCH(128, true, StBf16);
-            else if (h2 && tab) X3K_LAUNCH(128, true, StF32, true); else if (h2) X3K_LAUNCH(128, true); else X3K_LAUNCH(128, false);
-        }
-#undef X3K_LAUNCH
-        return x3_status();
-    }
-    // interleave: bit 0 = even / odd workgroup -> branch map; bit 1 = image-local map where the shapes allow it (else bit 0
-    // decides); bits 8.. = start skew of every other workgroup in units of 256 cycles
-    const int skew = (interleave >> 8) * 256;
-    auto wg_map = [&](int NL, int n0, int n1) {
-        if (n0 != n1) return 0;
-        const bool square = ba->B == bb->B && ba->M == bb->M && ba->N == bb->N && ba->M == ba->N && ba->axis != bb->axis;
-        if ((interleave & 2) && square && ba->B % 8 == 0 && ba->M % NL == 0) return 2 | ((ba->M / NL) << 8);
-        return (interleave & 1) ? 1 : 0;
-    };
-    if (x3_latency_tiles(a.R, b.R, ba->tile_lines, ba->storage)) {
-        const bool cs = x3_latency_split(a.R, b.R, ba->tile_lines, h2 && a.wpk && b.wpk);
-        const int n0 = (cs ? 2 : 1) * ((a.R + 3) / 4), n1 = (cs ? 2 : 1) * ((b.R + 3) / 4);
-        if (cs && a.dft && b.dft)
-            FFNO_LAUNCH((spectral_x3s_pair_kernel<true, true, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else if (cs)
-            FFNO_LAUNCH((spectral_x3s_pair_kernel<true, false, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else if (h2 && a.dft && b.dft)
-            FFNO_LAUNCH((spectral_x3s_pair_kernel<true, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else if (h2)
-            FFNO_LAUNCH((spectral_x3s_pair_kernel<true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        else
-            FFNO_LAUNCH((spectral_x3s_pair_kernel<false>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, n1);
-        return x3_status();
-    }
-    // <= 16 modes on the split-fp16 DFT with both branches' fragment tables (ffno_spectral_x3_dft_frags for the launch's direction):
-    // no wave rebuilds the DFT matrices from the twiddles (same values: results bit-identical with and without the tables)
-    const bool tab16 = h2 && a.wpk && b.wpk && a.dft && b.dft;
-    if (ba->storage == FFNO_STORE_BF16) {
-        if (x3_small_tiles(a.R, b.R, ba->tile_lines)) {
-            const int n0 = (a.R + 7) / 8, n1 = (b.R + 7) / 8, il = wg_map(8, n0, n1);
-            if (tab16)
-                FFNO_LAUNCH((spectral_x3_pair_kernel<8, true, StBf16, false, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-            else
-                FFNO_LAUNCH((spectral_x3_pair_kernel<8, true, StBf16>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-        } else {
-            const int n0 = (a.R + 15) / 16, n1 = (b.R + 15) / 16, il = wg_map(16, n0, n1);
-            if (tab16)
-                FFNO_LAUNCH((spectral_x3_pair_kernel<16, true, StBf16, false, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-            else
-                FFNO_LAUNCH((spectral_x3_pair_kernel<16, true, StBf16>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-        }
-        return x3_status();
-    }
-    if (x3_small_tiles(a.R, b.R, ba->tile_lines)) {
-        const int n0 = (a.R + 7) / 8, n1 = (b.R + 7) / 8, il = wg_map(8, n0, n1);
-        if (tab16)
-            FFNO_LAUNCH((spectral_x3_pair_kernel<8, true, StF32, false, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-        else if (h2)
-            FFNO_LAUNCH((spectral_x3_pair_kernel<8, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-        else
-            FFNO_LAUNCH((spectral_x3_pair_kernel<8, false>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-    } else {
-        const int n0 = (a.R + 15) / 16, n1 = (b.R + 15) / 16, il = wg_map(16, n0, n1);
-        if (tab16)
-            FFNO_LAUNCH((spectral_x3_pair_kernel<16, true, StF32, false, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-        else if (h2)
-            FFNO_LAUNCH((spectral_x3_pair_kernel<16, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-        else
-            FFNO_LAUNCH((spectral_x3_pair_kernel<16, false>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, skew);
-    }
-    return x3_status();
+    return x3_run(a, b, ba, bb, C, true, interleave, false, stream);
 }
 
 // ---- first kernel of the INFERENCE layer (infer.hip): both forward transforms + both channel mixes -> the mixed spectra -------
@@ -2816,33 +2807,12 @@ static int mix_pair_args(X3Args& a, X3Args& b, const ffno_fused_branch* ba, cons
 extern "C" int ffno_spectral_x3_mix_pair(const ffno_fused_branch* ba, const ffno_fused_branch* bb, int C, int interleave,
                                          void* stream) {
     X3Args a, b;
-    const int rca = mix_pair_args(a, b, ba, bb, C);
-    if (rca) return rca;
-    const size_t smem = sizeof(float) * 2 * max(a.L, b.L);
-    hipStream_t st = (hipStream_t)stream;
-    auto wg_map = [&](int NL, int n0, int n1) {
-        if (n0 != n1) return 0;
-        const bool square = ba->B == bb->B && ba->M == bb->M && ba->N == bb->N && ba->M == ba->N && ba->axis != bb->axis;
-        if ((interleave & 2) && square && ba->B % 8 == 0 && ba->M % NL == 0) return 2 | ((ba->M / NL) << 8);
-        return (interleave & 1) ? 1 : 0;
-    };
-    // both branches with a DFT-fragment table (ffno_spectral_x3_dft_frags; the second inference kernel needs them anyway): the forward
-    // fragments come from it instead of being rebuilt from the twiddles by every wave (same values: results bit-identical)
-    const bool tab = a.dft && b.dft;
-    if (x3_small_tiles(a.R, b.R, ba->tile_lines)) {
-        const int n0 = (a.R + 7) / 8, n1 = (b.R + 7) / 8, il = wg_map(8, n0, n1);
-        if (tab)
-            FFNO_LAUNCH((spectral_x3_pair_kernel<8, true, StF32, true, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, 0);
-        else
-            FFNO_LAUNCH((spectral_x3_pair_kernel<8, true, StF32, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, 0);
-    } else {
-        const int n0 = (a.R + 15) / 16, n1 = (b.R + 15) / 16, il = wg_map(16, n0, n1);
-        if (tab)
-            FFNO_LAUNCH((spectral_x3_pair_kernel<16, true, StF32, true, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, 0);
-        else
-            FFNO_LAUNCH((spectral_x3_pair_kernel<16, true, StF32, true>), dim3(n0 + n1), dim3(512), smem, st, a, b, n0, il, 0);
-    }
-    return x3_status();
+    const int rc = mix_pair_args(a, b, ba, bb, C);
+    if (rc) return rc;
+    // 8- or 16-line tiles, no skew.  Both branches with a DFT-fragment table (ffno_spectral_x3_dft_frags; the second inference kernel
+    // needs them anyway): the forward fragments come from it instead of being rebuilt from the twiddles by every wave (same values:
+    // results bit-identical)
+    return x3_run(a, b, ba, bb, C, true, interleave, true, stream);
 }
 
 // ---- the whole layer stack of a forward-only pass as ONE persistent launch (round 6) -----------------------------------------------
@@ -2991,6 +2961,23 @@ extern "C" size_t ffno_infer_stack_trace_words(int n_layers) {
     return n_layers > 0 ? (size_t)1 + (size_t)8 * 2 * n_layers * 12 * 2 : 0;
 }
 
+// the shipped instances of the persistent kernel: per members of an image's group, with and without the trace
+using InferStackFn = void (*)(InferStackArgs);
+struct InferStackRow {
+    int members;
+    InferStackFn traced, plain;
+};
+template <int GM>
+constexpr InferStackRow infer_stack_row() {
+    return {GM, infer_stack_kernel<2, true, GM>, infer_stack_kernel<2, false, GM>};
+}
+static const InferStackRow* infer_stack_instance(int members) {
+    static constexpr InferStackRow rows[] = {infer_stack_row<16>(), infer_stack_row<8>()};
+    for (const InferStackRow& r : rows)
+        if (r.members == members) return &r;
+    return nullptr;
+}
+
 extern "C" int ffno_infer_stack(const ffno_infer_stack_desc* d, void* stream) {
     if (!d || !d->layers || !d->last_out || !d->sync || d->a.in != d->b.in || !d->a.in) return FFNO_EINVAL;
     if (!(d->a.flags & FFNO_BRANCH_SELF_RANGE)) return FFNO_EINVAL;      // (no range words travel between the phases)
@@ -3028,13 +3015,10 @@ extern "C" int ffno_infer_stack(const ffno_infer_stack_desc* d, void* stream) {
     const size_t lds1 = sizeof(float) * ((size_t)NL1 * X3Cfg::LSF + 2 * (size_t)max(S.a.L, S.b.L));
     const size_t smem = max(lds1, infer_lds_bytes(S.f.R, S.f.N, true));
     hipStream_t st = (hipStream_t)stream;
-    // the four instances: (trace, members)
-    const void* fn = GM == 16 ? (trace ? reinterpret_cast<const void*>(infer_stack_kernel<2, true, 16>)
-                                       : reinterpret_cast<const void*>(infer_stack_kernel<2, false, 16>))
-                              : (trace ? reinterpret_cast<const void*>(infer_stack_kernel<2, true, 8>)
-                                       : reinterpret_cast<const void*>(infer_stack_kernel<2, false, 8>));
-    rc = GM == 16 ? (trace ? allow_dynamic_lds(infer_stack_kernel<2, true, 16>, smem) : allow_dynamic_lds(infer_stack_kernel<2, false, 16>, smem))
-                  : (trace ? allow_dynamic_lds(infer_stack_kernel<2, true, 8>, smem) : allow_dynamic_lds(infer_stack_kernel<2, false, 8>, smem));
+    const InferStackRow* k = infer_stack_instance(GM);
+    if (!k) return FFNO_EUNSUPPORTED;
+    const InferStackFn fn = trace ? k->traced : k->plain;
+    rc = allow_dynamic_lds(fn, smem);
     if (rc) return rc;
     if (hipMemsetAsync(d->sync, 0, sizeof(uint32_t) * (ffno_infer_stack_sync_words(B) + (trace ? ffno_infer_stack_trace_words(S.L) : 0)), st) !=
         hipSuccess)
@@ -3047,17 +3031,14 @@ extern "C" int ffno_infer_stack(const ffno_infer_stack_desc* d, void* stream) {
             (void)hipGetLastError();
             void* args[] = {&S};
             // one workgroup per CU, all resident at once (plat::launch_cooperative: the group barriers rely on it)
-            const int e = plat::launch_cooperative(fn, dim3(cus), dim3(512), args, smem, st);
+            const int e = plat::launch_cooperative(reinterpret_cast<const void*>(fn), dim3(cus), dim3(512), args, smem, st);
             return e == 0 ? x3_status() : e;
         }
     }
     S.use_xcc = 0, S.groups = B, S.groups_per_xcd = 0;      // one group per image, workgroup w = member w % GM of group w / GM
     for (int ph = 0; ph < 2 * S.L; ++ph) {
         S.phase_lo = ph, S.phase_hi = ph + 1;
-        if (GM == 16)
-            FFNO_LAUNCH((infer_stack_kernel<2, false, 16>), dim3(B * 16), dim3(512), smem, st, S);
-        else
-            FFNO_LAUNCH((infer_stack_kernel<2, false, 8>), dim3(B * 8), dim3(512), smem, st, S);
+        FFNO_LAUNCH((k->plain), dim3(B * GM), dim3(512), smem, st, S);      // (the instance without the trace, whatever mode & 2 says)
         rc = x3_status();
         if (rc) return rc;
     }

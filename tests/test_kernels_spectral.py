@@ -1099,6 +1099,67 @@ def test_spectral_x3_width32_dft_table_is_bit_identical(be, B, M, N, K, directio
             np.testing.assert_array_equal(a, b)
 
 
+@pytest.mark.parametrize("B,M,N,K", [(1, 8, 12, 3), (2, 16, 32, 8)])
+@pytest.mark.parametrize("direction", ["fwd", "adj"])
+@pytest.mark.parametrize("storage", ["f32", "bf16"])
+def test_spectral_x3_pair_dft_table_is_bit_identical(be, x3_tile, B, M, N, K, direction, storage):
+    """The paired launch of <= 16 modes on 8- and 16-line tiles (fp16x2 packs) loading its DFT-matrix fragments from both branches'
+    tables of ffno_spectral_x3_dft_frags against the pair that rebuilds them from the twiddles, and the pair where only branch a
+    brings a table (it rebuilds for both): outputs, saved spectra, range words bit for bit, and equal to the two single launches.
+    Ragged and whole tiles at both tile heights, a non-power-of-two length, K < L / 2 + 1; fp32 and bf16 storage."""
+    from fourierflow_amd._capi import FusedBranch
+    from test_storage_bf16 import FFNO_STORE_BF16, bf16_data, get16, put16      # (imports this module: not at module level)
+    C = 64
+    lib, p = be.lib, be.ptr
+    rs = np.random.RandomState(B + M + N + K)
+    b16 = storage == "bf16"
+    if b16:
+        (x_h, x), (r_h, _) = bf16_data(rs, (B, M, N, C)), bf16_data(rs, (B, M, N, C))
+        dx, dres = put16(be, x_h), put16(be, r_h)
+    else:
+        x, resid = (rs.standard_normal((B, M, N, C)).astype(np.float32) for _ in range(2))
+        dx, dres = be.put(x), be.put(resid)
+    dx32 = be.put(x) if b16 else dx      # (the range word of the input: from its values as floats)
+    xw = be.zeros(1, np.uint32)
+    assert lib.ffno_amax(p(dx32), x.size, p(xw), None) == 0
+    fwd_ck, inv_ck, conj = (0, 1, 0) if direction != "adj" else (1, 0, 1)
+    br, keep = [], []
+    for axis in (0, 1):
+        L = N if axis == 0 else M
+        assert K < L // 2 + 1
+        w = (rs.standard_normal((C, C, K, 2)) * 0.02).astype(np.float32)
+        pk_f, pk_a, kp = _x3_pack(be, w, K, fmt=1)
+        tw = be.twiddle(L)
+        tab = be.zeros((int(lib.ffno_spectral_x3_dft_frags_bytes(L, K)) // 4,), np.uint32)
+        assert lib.ffno_spectral_x3_dft_frags(p(tw), L, K, fwd_ck, inv_ck, p(tab), None) == 0
+        keep += [kp, tw, tab]
+        br.append(dict(axis=axis, R=B * M if axis == 0 else B * N, tw=tw, tab=tab, planes=pk_a if direction == "adj" else pk_f))
+
+    def run(tabs, paired):
+        if b16:
+            outs = [put16(be, np.zeros(x.shape, np.uint16)) for _ in range(2)]
+        else:
+            outs = [be.empty(x.shape), be.empty(x.shape)]
+        sv = [be.empty((K, b["R"], 2, C)) for b in br]
+        words = [be.zeros(1, np.uint32), be.zeros(1, np.uint32)]
+        ds = [FusedBranch(p(dx), p(outs[i]), p(dres) if i == 0 else None, p(sv[i]), p(b["planes"]), p(b["tw"]), B, M, N, K,
+                          b["axis"], 0, 1, x3_tile, p(xw), p(words[i]), FFNO_STORE_BF16 if b16 else 0, 0, p(b["tab"]) if tabs[i] else None)
+              for i, b in enumerate(br)]
+        if paired:
+            assert lib.ffno_spectral_x3_pair(ctypes.byref(ds[0]), ctypes.byref(ds[1]), C, fwd_ck, inv_ck, conj, 1, None) == 0
+        else:
+            for d in ds:
+                assert lib.ffno_spectral_x3(ctypes.byref(d), C, fwd_ck, inv_ck, conj, None) == 0
+        return [(get16(be, t) if b16 else be.get(t)).copy() for t in outs] + [be.get(t).copy() for t in sv] + \
+               [np.asarray(be.get(t)).copy() for t in words]
+
+    ref = run((False, False), False)                      # the two single launches
+    assert all(np.all(np.isfinite(a)) for a in ref[2 if b16 else 0:4]) and all(np.asarray(a).any() for a in ref)
+    for tabs in ((False, False), (True, True), (True, False)):
+        for a, b in zip(run(tabs, True), ref):
+            np.testing.assert_array_equal(a, b)
+
+
 def test_spectral_x3_support_matrix(be):
     lib = be.lib
     assert lib.ffno_spectral_x3_supported(64, 16, 64) == 1
