@@ -125,6 +125,19 @@ class TrDesc(C.Structure):
     _fields_ = [("src", P), ("dst", P), ("rows", C.c_int32), ("cols", C.c_int32)]
 
 
+class IPhiParams(C.Structure):
+    """Mirror of ``ffno_iphi_params`` (include/ffno.h); ``NAMES`` = the reference's parameter names in field order."""
+    NAMES = ("fc0.weight", "fc0.bias", "fc_code.weight", "fc_code.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias",
+             "fc3.weight", "fc3.bias", "fc4.weight", "fc4.bias")
+    _fields_ = [(n, P) for n in ("fc0_w", "fc0_b", "code_w", "code_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b",
+                                 "fc4_w", "fc4_b")]
+
+
+class PcHeadParams(C.Structure):
+    """Mirror of ``ffno_pchead_params`` (include/ffno.h)."""
+    _fields_ = [(n, P) for n in ("bs_w", "bs_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+
+
 SIGNATURES = {
     "ffno_build_target": (C.c_char_p, []),
     "ffno_abi_version": (I, []),
@@ -254,6 +267,14 @@ SIGNATURES = {
     "ffno_nudft_supported": (I, [I, I, I]),
     "ffno_nudft_modes": (I, [P, P, P, I, I, I, I, I, I, P]),
     "ffno_nudft_points": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "ffno_iphi_supported": (I, [I]),
+    "ffno_iphi_bwd_ws_floats": (SZ, [I, I, I]),
+    "ffno_iphi_fwd": (I, [P, P, P, P, P, P, I, I, I, P]),
+    "ffno_iphi_bwd": (I, [P, P, P, P, P, P, P, P, P, I, I, I, P]),
+    "ffno_pchead_supported": (I, [I, I, I]),
+    "ffno_pchead_partial_floats": (SZ, [I, I, I, I]),
+    "ffno_pchead_fwd": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "ffno_pchead_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
 }
 
 

@@ -10,7 +10,8 @@ What is NOT here is the reference's control plane: Hydra (the loader of fourierf
 interpolations), Lightning (the routines run their own fused step), wandb (one JSON line per logged step on stdout)
 and the dataset builders.  Batches therefore come from ``--data FILE.npz`` (arrays named like
 the builder's batches: ``x``/``y`` [, ``f``, ``mu``] for the Markov and mesh routines, ``data`` for the rollout routine;
-first axis = samples) or, without it, are synthetic N(0,1) fields of the configured geometry.
+``xy``/``rr``/``sigma`` for the point-cloud routine; first axis = samples) or, without it, are synthetic N(0,1) fields of the
+configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless ``--size``, ``rr`` [B, 42], ``sigma`` [B, n, 1]).
 """
 from __future__ import annotations
 
@@ -39,7 +40,7 @@ def _last_routine():
 def _kind(routine) -> str:
     name = type(routine).__name__
     return {"Grid2DMarkovExperiment": "markov", "Grid2DRolloutExperiment": "rollout",
-            "StructuredMeshExperiment": "mesh"}[name]
+            "StructuredMeshExperiment": "mesh", "PointCloudExperiment": "pointcloud"}[name]
 
 
 def _device(device: Optional[str]) -> torch.device:
@@ -80,7 +81,7 @@ class _Batches:
         if data is not None:
             with np.load(str(data)) as z:
                 self.arrays = {k: z[k].astype(np.float32) for k in z.files}
-            need = ("data",) if self.kind == "rollout" else ("x", "y")
+            need = {"rollout": ("data",), "pointcloud": ("xy", "rr", "sigma")}.get(self.kind, ("x", "y"))
             missing = [k for k in need if k not in self.arrays]
             if missing:
                 raise ValueError(f"{data}: arrays {missing} missing (found {sorted(self.arrays)})")
@@ -106,6 +107,9 @@ class _Batches:
         B, G, r = self.B, self.grid, self.routine
         if self.kind == "rollout":
             return dict(data=self._rand(B, G, G, 10 + r.n_steps))
+        if self.kind == "pointcloud":
+            n = self.size[0] if self.size else 972
+            return dict(xy=torch.rand(B, n, 2, generator=self.gen).to(self.dev), rr=self._rand(B, 42), sigma=self._rand(B, n, 1))
         if self.kind == "mesh":
             size = self.size or (G, G)
             cin = r.model.input_dim - len(size)
@@ -129,7 +133,7 @@ class _Batches:
 def _train_step(routine, kind, batch, epoch, step):
     if kind == "rollout":
         return routine.training_step(batch, step)[0]
-    if kind == "mesh":
+    if kind in ("mesh", "pointcloud"):
         return routine.training_step(batch, step)
     return routine.training_step(batch, epoch=epoch)
 
@@ -144,7 +148,7 @@ def _valid_loss(routine, kind, batch) -> float:
         with torch.no_grad():
             if kind == "rollout":
                 return float(routine.validation_step(batch)["valid_loss"].item())
-            if kind == "mesh":
+            if kind in ("mesh", "pointcloud"):
                 return float(routine.validation_step(batch).item())
             tr = routine.trainer()
             pred = routine._unshuffle(tr.engine.forward(routine._shuffle(routine._build_features(batch, add_noise=False)), False))
@@ -195,6 +199,8 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     routine = build_routine(cfg).to(dev)
     _LAST["routine"] = routine
     kind = _kind(routine)
+    if kind == "pointcloud" and world > 1:
+        raise NotImplementedError("PointCloudExperiment: data parallel training is not built (one process, one GPU)")
     batches = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial, rank=rank, world=world)
     # checkpoints and the log lines are rank 0's (every rank holds the same weights and the same global normaliser statistics)
     trial_dir = None if no_logging else _trial_dir(config_path.parent, trial, checkpoint_id, create=rank == 0)
@@ -314,6 +320,8 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
             if kind == "rollout":
                 routine.eval()
                 return routine._learning_step(b)[2]
+            if kind == "pointcloud":
+                return routine(b)
             return routine.trainer().predict(b["x"])
 
     run()       # warm-up (routine.warmup() in the reference)
@@ -324,7 +332,7 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     if dev.type == "cuda":
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    steps = (n_steps or getattr(routine, "n_steps", None) or 1) if kind != "mesh" else 1
+    steps = (n_steps or getattr(routine, "n_steps", None) or 1) if kind not in ("mesh", "pointcloud") else 1
     out = output or (ckpt.parent / "predictions.npz")
     np.savez(str(out), preds=preds.detach().cpu().numpy())
     print(json.dumps(dict(checkpoint=str(ckpt), predictions=str(out), shape=list(preds.shape),

@@ -28,11 +28,14 @@ TARGET_MAP = {
     "fourierflow.modules.FNOZongyi2DBlock": "fourierflow_amd.modules.FNOZongyi2DBlock",
     "fourierflow.modules.FNOMesh2D": "fourierflow_amd.modules.FNOMesh2D",
     "fourierflow.modules.FNOMesh3D": "fourierflow_amd.modules.FNOMesh3D",
+    "fourierflow.modules.FNOFactorizedPointCloud2D": "fourierflow_amd.modules.FNOFactorizedPointCloud2D",
+    "fourierflow.modules.IPhi": "fourierflow_amd.modules.IPhi",
     "fourierflow.modules.WNLinear": "fourierflow_amd.modules.WNLinear",
     "fourierflow.modules.Normalizer": "fourierflow_amd.modules.Normalizer",
     "fourierflow.routines.Grid2DMarkovExperiment": "fourierflow_amd.routines.Grid2DMarkovExperiment",
     "fourierflow.routines.Grid2DRolloutExperiment": "fourierflow_amd.routines.Grid2DRolloutExperiment",
     "fourierflow.routines.StructuredMeshExperiment": "fourierflow_amd.routines.StructuredMeshExperiment",
+    "fourierflow.routines.PointCloudExperiment": "fourierflow_amd.routines.PointCloudExperiment",
 }
 _INTERP = re.compile(r"^\$\{\s*([\w.]+)\s*:\s*(.*?)\s*\}$")
 
@@ -141,6 +144,8 @@ def build_routine(cfg: Dict[str, Any]):
     routine_kwargs = {}
     model_target = str((r.get("conv") or r.get("model") or {}).get("_target_", ""))
     baseline = model_target.endswith(("FNOZongyi2DBlock", "FNOMesh2D", "FNOMesh3D"))     # the StepLR (and Adam) users built here
+    if model_target.startswith("fourierflow.") and model_target not in TARGET_MAP:      # before the optimiser checks: name the model
+        raise NotImplementedError(f"{model_target} has no MI355X-native counterpart in fourierflow_amd (see DESIGN.md section 7)")
     if opt is not None:
         names = ("torch.optim.AdamW",) + (("torch.optim.Adam",) if model_target.endswith(("FNOMesh2D", "FNOMesh3D")) else ())
         if not isinstance(opt, Partial) or opt.func.name not in names:

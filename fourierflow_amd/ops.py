@@ -27,13 +27,19 @@ def _twiddle(L: int, device) -> torch.Tensor:
 
 
 _SP2D_WS = {}
+_SP2D_SRC = {}      # workspace key -> (weakref of the two weight tensors a version was declared for, generation)
+_SP2D_GEN = [0]
 
 
 def _spectral2d_workspace(x, w_y, w_x, modes):
     """The operator's workspace for a shape, kept per (shape, device): besides the scratch spectra it holds the packed weight sets
     of the fused kernels (ffno_spectral2d_path), and the library reuses them across calls when the caller declares the VERSION of
     the weights (include/ffno.h: ffno_spectral2d_weights_version) -- here (data pointer, torch version counter) of both tensors, so
-    a forward / backward pair and repeated calls on unchanged weights pack once, and an optimizer step re-packs."""
+    a forward / backward pair and repeated calls on unchanged weights pack once, and an optimizer step re-packs.  A tensor that
+    was freed can hand its address AND its version count to a new one (the caching allocator reuses blocks; a fresh parameter starts
+    at the same small count), so the declared version also carries a generation that advances whenever the weight OBJECTS differ
+    from the ones the last version was declared for."""
+    import weakref
     lib = _lib.get_lib()
     B, M, N, C = x.shape
     key = (B, M, N, C, modes, str(x.device), _lib.is_test_backend())
@@ -46,7 +52,13 @@ def _spectral2d_workspace(x, w_y, w_x, modes):
     version = 0
     if w_y is not None and w_x is not None:
         try:
-            version = (hash((w_y.data_ptr(), w_y._version, w_x.data_ptr(), w_x._version)) & 0x7FFFFFFFFFFFFFFF) or 1
+            src = _SP2D_SRC.get(key)
+            if src is None or src[0]() is not w_y or src[1]() is not w_x:
+                _SP2D_GEN[0] += 1
+                src = _SP2D_SRC[key] = (weakref.ref(w_y), weakref.ref(w_x), _SP2D_GEN[0])
+                for k in [k for k in _SP2D_SRC if k not in _SP2D_WS]:
+                    del _SP2D_SRC[k]
+            version = (hash((w_y.data_ptr(), w_y._version, w_x.data_ptr(), w_x._version, src[2])) & 0x7FFFFFFFFFFFFFFF) or 1
         except RuntimeError:        # inference tensors have no version counter: undeclared, the library packs on every call
             version = 0
     _capi.check(lib.ffno_spectral2d_weights_version(_p(ws), version), "spectral2d_weights_version")
@@ -384,3 +396,258 @@ def point_ifft2d(spec, xi):
     B, C, R, m2 = spec.shape
     _nudft_check(xi, B, xi.shape[1] if xi.dim() == 3 else -1, C, R // 2, m2)
     return _PointIFFT2dFn.apply(sr.contiguous(), xi.contiguous())
+
+
+# ---- grid <-> corner modes: the two ends of the point-cloud F-FNO's latent grid (rfft2 / irfft2 restricted to the kept corners) ----
+# Mode-major spectra are the grid kernels' layout: Z[ky][kx'][b][re/im][c], kx' < m1 the rows k1 = kx', kx' >= m1 the rows
+# k1 = kx' - 2 m1; the non-uniform DFT's layout is [b][c][kx'][ky][re/im].  The kernels' twiddle tables carry 1 / sqrt(L) per
+# axis (norm='ortho'), so torch's default normalisations (1 for rfft2, 1 / (s1 s2) for irfft2) are a factor sqrt(s1 s2) away.
+
+def _corner_guard(m1, m2, s1, s2, C):
+    if m1 < 1 or m2 < 1 or 2 * m1 > s1 or m2 > s2 // 2 or m1 > min(s1, s2) // 2 + 1:
+        raise ValueError(f"modes ({m1}, {m2}) do not fit a {s1} x {s2} latent grid (need 2 modes1 <= s1, modes2 <= s2 // 2, "
+                         f"modes1 <= min(s1, s2) // 2 + 1)")
+    if C not in (32, 64):
+        raise ValueError(f"width {C} is outside the compiled channel tiles (32 / 64)")
+
+
+def _modes_major(spec_r):
+    """[B, C, 2 m1, m2, 2] -> [m2, 2 m1, B, 2, C]"""
+    return spec_r.permute(3, 2, 0, 4, 1)
+
+
+def _points_major(z):
+    """[m2, 2 m1, B, 2, C] -> [B, C, 2 m1, m2, 2]"""
+    return z.permute(2, 4, 1, 0, 3)
+
+
+class _ModesToGridFn(torch.autograd.Function):
+    """Z [m2, 2 m1, B, 2, C] (mode-major corners) -> channels-last grid [B, s1, s2, C] = irfft2 of the zero-padded spectrum."""
+
+    @staticmethod
+    def forward(ctx, z, s1, s2):
+        lib = _lib.get_lib()
+        m2, R, B, _, C = z.shape
+        m1 = R // 2
+        st = _lib.current_stream(z.device)
+        f32 = dict(dtype=torch.float32, device=z.device)
+        zs = (z * (1.0 / float(np.sqrt(s1 * s2)))).contiguous()
+        cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
+        sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
+        out = torch.empty(B, s1, s2, C, **f32)
+        _capi.check(lib.ffno_cdft_rows_mfma(_p(zs), _p(sy), _p(cw), _p(_twiddle(s1, z.device)), B, s1, C, m1, m2, 1, st), "cdft_rows")
+        _capi.check(lib.ffno_dft_inv(_p(sy), _p(out), None, _p(_twiddle(s2, z.device)), B, s1, s2, C, m2, 0, 1, 0, st), "dft_inv")
+        ctx.cfg = (s1, s2, m1, m2, B, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.get_lib()
+        s1, s2, m1, m2, B, C = ctx.cfg
+        g = g.contiguous()
+        st = _lib.current_stream(g.device)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
+        sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
+        dz = torch.empty(m2, 2 * m1, B, 2, C, **f32)
+        # the adjoint of the zero-padded irfft (bins k >= 1 counted twice), then the adjoint of the inverse row transform
+        _capi.check(lib.ffno_dft_fwd(_p(g), _p(sy), _p(_twiddle(s2, g.device)), B, s1, s2, C, m2, 0, 1, st), "dft_fwd")
+        _capi.check(lib.ffno_cdft_rows_mfma(_p(sy), _p(dz), _p(cw), _p(_twiddle(s1, g.device)), B, s1, C, m1, m2, 0, st), "cdft_rows")
+        return dz * (1.0 / float(np.sqrt(s1 * s2))), None, None
+
+
+class _GridToMixedModesFn(torch.autograd.Function):
+    """Channels-last grid [B, s1, s2, C] -> mode-major corners of rfft2 mixed with the two corner weight tensors
+    ([C, C, m1, m2, 2] each, `bixy,ioxy->boxy`): [m2, 2 m1, B, 2, C]."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2):
+        lib = _lib.get_lib()
+        B, s1, s2, C = x.shape
+        m1, m2 = w1.shape[2], w1.shape[3]
+        K = 2 * m1 * m2
+        st = _lib.current_stream(x.device)
+        f32 = dict(dtype=torch.float32, device=x.device)
+        wp, wpt = torch.empty(2 * K * C * C, **f32), torch.empty(2 * K * C * C, **f32)
+        _capi.check(lib.ffno_fw2d_pack2(_p(w1), _p(w2), _p(wp), _p(wpt), C, m1, m2, st), "fw2d_pack2")
+        cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
+        sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
+        sx, out = torch.empty(K * B * 2 * C, **f32), torch.empty(m2, 2 * m1, B, 2, C, **f32)
+        _capi.check(lib.ffno_dft_fwd(_p(x), _p(sy), _p(_twiddle(s2, x.device)), B, s1, s2, C, m2, 0, 0, st), "dft_fwd")
+        _capi.check(lib.ffno_cdft_rows_mfma(_p(sy), _p(sx), _p(cw), _p(_twiddle(s1, x.device)), B, s1, C, m1, m2, 0, st), "cdft_rows")
+        _capi.check(lib.ffno_mode_mix(_p(sx), _p(wp), _p(out), B, C, K, 0, st), "mode_mix")
+        ctx.save_for_backward(sx, wpt)
+        ctx.cfg = (B, s1, s2, C, m1, m2)
+        return out * float(np.sqrt(s1 * s2))
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.get_lib()
+        sx, wpt = ctx.saved_tensors
+        B, s1, s2, C, m1, m2 = ctx.cfg
+        K = 2 * m1 * m2
+        st = _lib.current_stream(g.device)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        dy = (g * float(np.sqrt(s1 * s2))).contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dsx = torch.empty(K * B * 2 * C, **f32)
+            cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
+            sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
+            dx = torch.empty(B, s1, s2, C, **f32)
+            _capi.check(lib.ffno_mode_mix(_p(dy), _p(wpt), _p(dsx), B, C, K, 1, st), "mode_mix")
+            _capi.check(lib.ffno_cdft_rows_mfma(_p(dsx), _p(sy), _p(cw), _p(_twiddle(s1, g.device)), B, s1, C, m1, m2, 1, st),
+                        "cdft_rows")
+            _capi.check(lib.ffno_dft_inv(_p(sy), _p(dx), None, _p(_twiddle(s2, g.device)), B, s1, s2, C, m2, 0, 0, 0, st), "dft_inv")
+        part = torch.empty(2 * K * C * C, **f32)
+        gw1, gw2 = torch.empty(C, C, m1, m2, 2, **f32), torch.empty(C, C, m1, m2, 2, **f32)
+        n = K * B * 2 * C
+        _capi.check(lib.ffno_fw_grad_partial(_p(sx), _p(dy), _p(part), B, C, K, 1, 0, 1, n, n, st), "fw_grad_partial")
+        _capi.check(lib.ffno_fw2d_grad_reduce2(_p(part), _p(gw1), _p(gw2), C, m1, m2, 1, 0, st), "fw2d_grad_reduce2")
+        return dx, gw1, gw2
+
+
+def modes_to_grid(z, s1: int, s2: int):
+    """Mode-major corners [m2, 2 m1, B, 2, C] -> [B, s1, s2, C] (see corners_to_grid)."""
+    _lib.require_device_tensor(z, "corner modes")
+    if z.dim() != 5 or z.shape[1] % 2 or z.shape[3] != 2:
+        raise ValueError(f"expected mode-major corners [m2, 2 m1, B, 2, C], got {tuple(z.shape)}")
+    _corner_guard(z.shape[1] // 2, z.shape[0], s1, s2, z.shape[4])
+    return _ModesToGridFn.apply(z, int(s1), int(s2))
+
+
+def corners_to_grid(spec, s1: int, s2: int):
+    """The x_out = None branch of the point-cloud SpectralConv2d (reference point_cloud_2d.py:70-74): complex64 corners
+    [B, C, 2 modes1, modes2] in point_fft2d's layout are placed in rows [0, m1) and [s1 - m1, s1), columns [0, m2) of an
+    s1 x (s2 // 2 + 1) spectrum and transformed by ``torch.fft.irfft2(., s=(s1, s2))`` -> channels-last real [B, s1, s2, C]."""
+    if not isinstance(spec, torch.Tensor) or spec.dtype != torch.complex64 or spec.dim() != 4:
+        raise TypeError("spec: expected a complex64 tensor [B, C, 2 m1, m2]")
+    return modes_to_grid(_modes_major(torch.view_as_real(spec)), s1, s2)
+
+
+def grid_to_mixed_modes(x, w1, w2):
+    """Channels-last grid -> mixed mode-major corners (see grid_to_mixed_corners); w1 / w2 real views [C, C, m1, m2, 2]."""
+    _lib.require_device_tensor(x, "grid")
+    if x.dim() != 4 or w1.shape != w2.shape or w1.dim() != 5 or w1.shape[0] != x.shape[3] or w1.shape[1] != x.shape[3]:
+        raise ValueError(f"expected x [B, s1, s2, C] and two weights [C, C, m1, m2, 2], got {tuple(x.shape)}, {tuple(w1.shape)}")
+    _corner_guard(w1.shape[2], w1.shape[3], x.shape[1], x.shape[2], x.shape[3])
+    return _GridToMixedModesFn.apply(x.contiguous(), w1.contiguous(), w2.contiguous())
+
+
+def grid_to_mixed_corners(x, weights1, weights2):
+    """The x_in = None branch of the point-cloud SpectralConv2d up to the concatenation (reference point_cloud_2d.py:49, :60-63,
+    :76): ``torch.fft.rfft2`` of the channels-last grid x [B, s1, s2, C], rows [:m1] mixed with weights1 and rows [-m1:] with
+    weights2 (`bixy,ioxy->boxy`, columns [:m2]; complex64 [C, C, m1, m2] or their view_as_real twins), concatenated ->
+    complex64 [B, C, 2 m1, m2], what point_ifft2d takes.  Differentiable in x and both weights."""
+    w1 = torch.view_as_real(weights1) if weights1.is_complex() else weights1
+    w2 = torch.view_as_real(weights2) if weights2.is_complex() else weights2
+    return torch.view_as_complex(_points_major(grid_to_mixed_modes(x, w1, w2)).contiguous())
+
+
+# ---- the two per-point networks of the elasticity F-FNO ---------------------------------------------------------------------
+def _param_struct(cls, tensors):
+    return cls(*[t.data_ptr() for t in tensors])
+
+
+class _IPhiFn(torch.autograd.Function):
+    """xi = IPhi(x, code) (csrc/ffno_iphi.h); params in _capi.IPhiParams.NAMES order."""
+
+    @staticmethod
+    def forward(ctx, x, code, width, *params):
+        lib = _lib.get_lib()
+        B, N = x.shape[:2]
+        need = any(ctx.needs_input_grad)
+        f32 = dict(dtype=torch.float32, device=x.device)
+        xi = torch.empty_like(x)
+        feat = torch.empty(B * N, 4, **f32) if need else None
+        acts = torch.empty(4, B * N, 4 * width, **f32) if need else None
+        par = _param_struct(_capi.IPhiParams, params)
+        _capi.check(lib.ffno_iphi_fwd(ctypes.byref(par), _p(x), _p(code), _p(xi), _p(feat), _p(acts), B, N, width,
+                                      _lib.current_stream(x.device)), "iphi_fwd")
+        if need:
+            ctx.save_for_backward(x, code, feat, acts, *params)
+        ctx.width = width
+        return xi
+
+    @staticmethod
+    def backward(ctx, dxi):
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("IPhi: the gradient with respect to the input coordinates is not computed by the gfx950 kernel set "
+                               "(feed it a tensor that does not require grad)")
+        x, code, feat, acts, *params = ctx.saved_tensors
+        lib = _lib.get_lib()
+        B, N = x.shape[:2]
+        width = ctx.width
+        dxi = dxi.contiguous()
+        grads = [torch.empty_like(p) for p in params]
+        dcode = torch.empty_like(code)
+        ws = torch.empty(int(lib.ffno_iphi_bwd_ws_floats(B, N, width)), dtype=torch.float32, device=x.device)
+        par, gpar = _param_struct(_capi.IPhiParams, params), _param_struct(_capi.IPhiParams, grads)
+        _capi.check(lib.ffno_iphi_bwd(ctypes.byref(par), ctypes.byref(gpar), _p(x), _p(code), _p(feat), _p(acts), _p(dxi),
+                                      _p(dcode), _p(ws), B, N, width, _lib.current_stream(x.device)), "iphi_bwd")
+        return (None, dcode if ctx.needs_input_grad[1] else None, None, *grads)
+
+
+def iphi_forward(x, code, width: int, params):
+    """``IPhi.forward(x, code)`` (reference modules/iphi.py:27-58): x [B, N, 2], code [B, 42] -> xi [B, N, 2]; ``params`` = the
+    twelve tensors of fc0, fc_code, fc1..fc4 (weight, bias each).  Differentiable in the parameters and in code."""
+    _lib.require_device_tensor(x, "IPhi input")
+    _lib.require_device_tensor(code, "IPhi code")
+    if x.dim() != 3 or x.shape[2] != 2 or code.dim() != 2 or code.shape[0] != x.shape[0] or code.shape[1] != 42:
+        raise ValueError(f"expected x [B, N, 2] and code [B, 42], got {tuple(x.shape)} and {tuple(code.shape)}")
+    if not _lib.get_lib().ffno_iphi_supported(width):
+        raise ValueError(f"IPhi width {width} is outside the compiled set (16, 32, 64)")
+    return _IPhiFn.apply(x.contiguous(), code.contiguous(), int(width), *[p.contiguous() for p in params])
+
+
+class _PointHeadFn(torch.autograd.Function):
+    """y = fc2(gelu(fc1(t + bs x + b))) on channel-major t (csrc/ffno_pchead.h)."""
+
+    @staticmethod
+    def forward(ctx, t, x, *params):
+        lib = _lib.get_lib()
+        B, W, N = t.shape
+        O = params[4].shape[0]
+        need = any(ctx.needs_input_grad)
+        y = torch.empty(B, N, O, dtype=torch.float32, device=t.device)
+        pre = torch.empty(B * N, 128, dtype=torch.float32, device=t.device) if need else None
+        par = _param_struct(_capi.PcHeadParams, params)
+        _capi.check(lib.ffno_pchead_fwd(ctypes.byref(par), _p(t), _p(x), _p(y), _p(pre), B, N, W, O, _lib.current_stream(t.device)),
+                    "pchead_fwd")
+        if need:
+            ctx.save_for_backward(t, x, pre, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError("point head: the gradient with respect to the output coordinates is not computed by the gfx950 "
+                               "kernel set (feed it a tensor that does not require grad)")
+        t, x, pre, *params = ctx.saved_tensors
+        lib = _lib.get_lib()
+        B, W, N = t.shape
+        O = params[4].shape[0]
+        dy = dy.contiguous()
+        grads = [torch.empty_like(p) for p in params]
+        dt = torch.empty_like(t)
+        part = torch.empty(int(lib.ffno_pchead_partial_floats(B, N, W, O)), dtype=torch.float32, device=t.device)
+        par, gpar = _param_struct(_capi.PcHeadParams, params), _param_struct(_capi.PcHeadParams, grads)
+        _capi.check(lib.ffno_pchead_bwd(ctypes.byref(par), ctypes.byref(gpar), _p(t), _p(x), _p(dy), _p(pre), _p(dt), _p(part), B, N,
+                                        W, O, _lib.current_stream(t.device)), "pchead_bwd")
+        return (dt, None, *grads)
+
+
+def point_head(t, x_out, bs, fc1, fc2):
+    """The output head of FNOFactorizedPointCloud2D (reference point_cloud_2d.py:263-270): t [B, W, N] channel-major (what
+    point_ifft2d returns), x_out [B, N, 2], bs = nn.Conv1d(2, W, 1), fc1 = nn.Linear(W, 128), fc2 = nn.Linear(128, out)
+    -> [B, N, out]."""
+    _lib.require_device_tensor(t, "point features")
+    _lib.require_device_tensor(x_out, "x_out")
+    B, W, N = t.shape
+    if x_out.shape != (B, N, 2):
+        raise ValueError(f"x_out: expected [{B}, {N}, 2], got {tuple(x_out.shape)}")
+    if not _lib.get_lib().ffno_pchead_supported(W, fc1.out_features, fc2.out_features):
+        raise ValueError(f"point head (width {W}, hidden {fc1.out_features}, out {fc2.out_features}) is outside the compiled set "
+                         "(width 32 / 64, hidden 128, out 1..64)")
+    params = [bs.weight.reshape(W, 2), bs.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias]
+    return _PointHeadFn.apply(t.contiguous(), x_out.contiguous(), *[p.contiguous() for p in params])

@@ -947,6 +947,58 @@ int ffno_nudft_modes(const float* u, const float* xi, float* spec, int B, int C,
 int ffno_nudft_points(const float* spec, const float* xi, const float* w, float* out, float* dxi, int B, int C, int N,
                       int m1, int m2, int quirk, int accumulate, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * IPhi, the coordinate deformation network of the elasticity F-FNO (reference fourierflow/modules/iphi.py:27-58, the
+ * `code` branch: feature engineering :32-34, NeRF features :37-39, fc0 / fc_code and the two concatenations :40-46, fc1..fc4
+ * with tanh :51-57, x + x * xd :58).  x[B][N][2], code[B][42], width w in {16, 32, 64} (ffno_iphi_supported), H = 4 w.
+ * Parameters in nn.Linear layout ([out][in] weights); the same struct carries the gradient pointers of ffno_iphi_bwd.
+ *   ffno_iphi_fwd: xi[B][N][2].  Optional outputs: feat[B N][4] = (x0, x1, angle, radius) as the kernel computed them
+ *       (diagnostics / parity tests; ffno_iphi_bwd reads it), acts[4][B N][H] = the inputs of fc1..fc4 (what the backward
+ *       pass needs; NULL for inference).  One launch; the H x H layers are exact-fp32 MFMA.
+ *   ffno_iphi_bwd: from dxi, every gradient of fc0, fc_code, fc1..fc4 (written, not accumulated) and dcode[B][42].  The
+ *       gradient with respect to x is not produced.  ws: ffno_iphi_bwd_ws_floats() floats.  Deterministic: fixed point
+ *       slices, summed in a fixed order, no atomics.
+ * fc_no_code (iphi.py:48, code = None) has no kernel.
+ * --------------------------------------------------------------------------------------------- */
+#define FFNO_IPHI_CODE_DIM 42
+typedef struct ffno_iphi_params {
+    float *fc0_w, *fc0_b;   /* [w][4], [w]   */
+    float *code_w, *code_b; /* [w][42], [w]  */
+    float *fc1_w, *fc1_b;   /* [H][H], [H]   */
+    float *fc2_w, *fc2_b;
+    float *fc3_w, *fc3_b;
+    float *fc4_w, *fc4_b;   /* [2][H], [2]   */
+} ffno_iphi_params;
+int ffno_iphi_supported(int width);
+size_t ffno_iphi_bwd_ws_floats(int B, int N, int width);
+int ffno_iphi_fwd(const ffno_iphi_params* params, const float* x, const float* code, float* xi, float* feat, float* acts, int B,
+                  int N, int width, void* stream);
+int ffno_iphi_bwd(const ffno_iphi_params* params, const ffno_iphi_params* grads, const float* x, const float* code,
+                  const float* feat, const float* acts, const float* dxi, float* dcode, float* ws, int B, int N, int width,
+                  void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Output head of FNOFactorizedPointCloud2D (reference point_cloud_2d.py:263-270: bs[-1](x_out.permute), the add, the
+ * permute, fc1, F.gelu, fc2) on the channel-major point features t[B][W][N] that ffno_nudft_points writes:
+ *     y[b][n][:] = fc2(gelu(fc1(t[b][:][n] + bs_w x[b][n] + bs_b)))       x[B][N][2], y[B][N][out_channels]
+ * W in {32, 64}, hidden 128, 1 <= out_channels <= 64 (ffno_pchead_supported).  bs_w[W][2] is the Conv1d weight [W, 2, 1].
+ *   ffno_pchead_fwd: y; optional pre[B N][128] = fc1's output before the GELU (what the backward pass reads).
+ *   ffno_pchead_bwd: dt[B][W][N] (channel-major again: it feeds the adjoint of ifft2d) and the six parameter gradients
+ *       (written, not accumulated).  partial: ffno_pchead_partial_floats() floats.  Deterministic, no atomics.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct ffno_pchead_params {
+    float *bs_w, *bs_b;   /* [W][2], [W]              */
+    float *fc1_w, *fc1_b; /* [128][W], [128]          */
+    float *fc2_w, *fc2_b; /* [out][128], [out]        */
+} ffno_pchead_params;
+int ffno_pchead_supported(int W, int hidden, int out_channels);
+size_t ffno_pchead_partial_floats(int B, int N, int W, int out_channels);
+int ffno_pchead_fwd(const ffno_pchead_params* params, const float* t, const float* x, float* y, float* pre, int B, int N, int W,
+                    int out_channels, void* stream);
+int ffno_pchead_bwd(const ffno_pchead_params* params, const ffno_pchead_params* grads, const float* t, const float* x,
+                    const float* dy, const float* pre, float* dt, float* partial, int B, int N, int W, int out_channels,
+                    void* stream);
+
 /* small utilities used by the host driver */
 int ffno_axpy(float* y, const float* x, float alpha, size_t n, void* stream); /* y += alpha*x */
 
