@@ -261,6 +261,9 @@ SIGNATURES = {
     "ffno_lploss_tmp_floats": (SZ, [I, I]),
     "ffno_lploss_fwd_bwd": (I, [P, P, P, P, P, I, I, F, P, P]),
     "ffno_markov_features": (I, [P, P, P, P, P, P, I, I, I, I, F, F, F, F, I, I, P, P]),
+    "ffno_markov_traj_ws_floats": (SZ, [I, I, I, I]),
+    "ffno_markov_traj_step": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
+    "ffno_markov_traj_metrics": (I, [P, P, I, I, I, I, F, P]),
     "ffno_adamw_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_adam_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_axpy": (I, [P, P, F, SZ, P]),

@@ -10,6 +10,8 @@ What is NOT here is the reference's control plane: Hydra (the loader of fourierf
 interpolations), Lightning (the routines run their own fused step), wandb (one JSON line per logged step on stdout)
 and the dataset builders.  Batches therefore come from ``--data FILE.npz`` (arrays named like
 the builder's batches: ``x``/``y`` [, ``f``, ``mu``] for the Markov and mesh routines, ``data`` for the rollout routine;
+for the Markov routine a file with ``data`` [n, M, N, T] [, ``times``, ``f``, ``mu``, ``corr_data``] is a TRAJECTORY file, what
+its validation / test loaders deliver: `test --data` and `train --valid-data` run the autoregressive metrics on it;
 ``xy``/``rr``/``sigma`` for the point-cloud routine; first axis = samples) or, without it, are synthetic N(0,1) fields of the
 configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless ``--size``, ``rr`` [B, 42], ``sigma`` [B, n, 1]).
 """
@@ -82,6 +84,12 @@ class _Batches:
             with np.load(str(data)) as z:
                 self.arrays = {k: z[k].astype(np.float32) for k in z.files}
             need = {"rollout": ("data",), "pointcloud": ("xy", "rr", "sigma")}.get(self.kind, ("x", "y"))
+            if self.kind == "markov" and "data" in self.arrays:       # whole trajectories [n, M, N, T]: validation / test batches
+                if self.arrays["data"].ndim != 4:
+                    raise ValueError(f"{data}: a trajectory file holds data [n, M, N, T], got {self.arrays['data'].shape}")
+                if len(self.arrays["data"]) < self.B:
+                    raise ValueError(f"{data}: {len(self.arrays['data'])} trajectories do not fill one batch of {self.B}")
+                need = ("data",)
             missing = [k for k in need if k not in self.arrays]
             if missing:
                 raise ValueError(f"{data}: arrays {missing} missing (found {sorted(self.arrays)})")
@@ -129,6 +137,10 @@ class _Batches:
             return dict(x=xx, y=d[..., 10:].contiguous())
         return b
 
+    @property
+    def trajectories(self) -> bool:
+        return self.kind == "markov" and self.arrays is not None and "data" in self.arrays
+
 
 def _train_step(routine, kind, batch, epoch, step):
     if kind == "rollout":
@@ -150,6 +162,8 @@ def _valid_loss(routine, kind, batch) -> float:
                 return float(routine.validation_step(batch)["valid_loss"].item())
             if kind in ("mesh", "pointcloud"):
                 return float(routine.validation_step(batch).item())
+            if "data" in batch:      # a trajectory batch: the reference's valid_loss, over the autoregressive rollout (:392-403)
+                return float(routine.validation_step(batch)["valid_loss"])
             tr = routine.trainer()
             pred = routine._unshuffle(tr.engine.forward(routine._shuffle(routine._build_features(batch, add_noise=False)), False))
             target = (batch["dy"] if routine.learn_difference else batch["y"]).contiguous()
@@ -190,6 +204,9 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
           accumulation_batches: int = Option(4, help="epoch-0 batches that only accumulate the normaliser statistics"),
           steps_per_epoch: int = Option(0, help="advance the epoch counter (StepLR, file names) every N steps; 0 = never"),
           data: Optional[Path] = Option(None, help=".npz with the builder's batch arrays; default: synthetic fields"),
+          valid_data: Optional[Path] = Option(None, help="Markov routine: .npz of whole trajectories (data [n, M, N, T] [, times, "
+                                                         "f, mu, corr_data]); valid_loss becomes the trajectory loss of "
+                                                         "validation_step over its first batch"),
           batch_size: Optional[int] = None, grid: int = 64, size: Optional[List[int]] = Option(None, help="mesh size"),
           device: Optional[str] = Option(None, hidden=True)):
     """Train: build the routine from CONFIG (+ `a.b=c` overrides) and run fused optimisation steps."""
@@ -202,6 +219,16 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     if kind == "pointcloud" and world > 1:
         raise NotImplementedError("PointCloudExperiment: data parallel training is not built (one process, one GPU)")
     batches = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial, rank=rank, world=world)
+    if batches.trajectories:
+        raise ValueError(f"{data}: a trajectory file cannot be trained on (training takes x / y pairs); pass it as --valid-data")
+    valid_batch = None
+    if valid_data is not None:
+        if kind != "markov":
+            raise ValueError("--valid-data takes the Markov routine's trajectory files; the other routines validate on --data")
+        valid = _Batches(routine, cfg, dev, valid_data, batch_size, grid, size, seed=7231 + trial)
+        if not valid.trajectories:
+            raise ValueError(f"{valid_data}: no `data` [n, M, N, T] array (found {sorted(valid.arrays)})")
+        valid_batch = next(iter(valid))
     # checkpoints and the log lines are rank 0's (every rank holds the same weights and the same global normaliser statistics)
     trial_dir = None if no_logging else _trial_dir(config_path.parent, trial, checkpoint_id, create=rank == 0)
     out_dir = trial_dir if rank == 0 else None      # (only rank 0 writes; every rank reads the checkpoint it resumes from)
@@ -252,7 +279,7 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
                    resumed_from_step=start["global_step"])
     if out_dir is not None:
         gs = start["global_step"] + steps
-        vl = _valid_loss(routine, kind, next(it))
+        vl = _valid_loss(routine, kind, valid_batch if valid_batch is not None else next(it))
         for old in out_dir.glob("epoch*.ckpt"):      # CustomModelCheckpoint keeps the single best file
             old.unlink()
         best = out_dir / f"epoch={epoch}-step={gs}-valid_loss={vl:.5f}.ckpt"
@@ -287,6 +314,9 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
         b = next(it)
         if kind == "rollout":
             m = {k: v for k, v in routine.test_step(b).items() if k in ("test_loss", "test_loss_avg", "test_time_until")}
+        elif src.trajectories:      # the reference's test metrics of the Markov routine (:408-416)
+            m = {k: v for k, v in routine.test_step(b).items()
+                 if k in ("test_loss", "test_loss_avg", "test_time_until", "test_corr")}
         else:
             m = {"test_loss": _valid_loss(routine, kind, b)}
         for k, v in m.items():

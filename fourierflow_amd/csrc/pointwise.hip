@@ -579,6 +579,95 @@ __global__ __launch_bounds__(256) void lploss_grad_kernel(const float* __restric
     }
 }
 
+// ---- Markov trajectory validation ---------------------------------------------------------------------------
+// One launch per rollout step: block (slice, sample) turns the model output into the prediction P, writes it twice (next
+// input, public preds) and leaves its six partial sums in sums[((t B + sample) S + slice) 6 ..]; the metrics kernel adds the S
+// partials of a sample in slice order.  data is time-last, so its two reads per element are 4-byte accesses T floats apart.
+static constexpr int kTrajSums = 6;
+
+__global__ __launch_bounds__(256) void markov_traj_step_kernel(const float* __restrict__ out, const float* __restrict__ affine,
+                                                               const float* prev, const float* __restrict__ data, float* im,
+                                                               float* __restrict__ preds, float* __restrict__ sums, int n, int T,
+                                                               int n_steps, int t) {
+    __shared__ float red[4][kTrajSums];
+    const int bidx = blockIdx.y, S = gridDim.x, B = gridDim.y;
+    const int chunk = (n + S - 1) / S;
+    const int beg = blockIdx.x * chunk, end = min(n, beg + chunk);
+    const float sc = affine ? affine[0] : 1.f, sh = affine ? affine[1] : 0.f;   // Normalizer.inverse(channel=0)
+    // the reference indexes yy[..., t - 1] with t = 0 as Python's -1: the difference target of step 0 is taken against the LAST step
+    const int tc = T - n_steps + t, tp = T - n_steps + (t > 0 ? t - 1 : n_steps - 1);
+    float s[kTrajSums];
+    FFNO_UNROLL
+    for (int k = 0; k < kTrajSums; ++k) s[k] = 0.f;
+    for (int i = beg + threadIdx.x; i < end; i += 256) {
+        const long e = (long)bidx * n + i;
+        const float raw = affine ? fmaf(out[e], sc, sh) : out[e];
+        const float yt = data[e * T + tc];
+        const float y = prev ? yt - data[e * T + tp] : yt;
+        const float P = prev ? prev[e] + raw : raw;
+        im[e] = P;
+        preds[e * n_steps + t] = P;
+        const float d = raw - y, dp = P - yt;
+        s[0] = fmaf(d, d, s[0]);
+        s[1] = fmaf(y, y, s[1]);
+        s[2] = fmaf(P, P, s[2]);
+        s[3] = fmaf(yt, yt, s[3]);
+        s[4] = fmaf(P, yt, s[4]);
+        s[5] = fmaf(dp, dp, s[5]);
+    }
+    FFNO_UNROLL
+    for (int k = 0; k < kTrajSums; ++k) {
+        s[k] = wave_sum(s[k]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < kTrajSums) {
+        const int k = threadIdx.x;
+        sums[(((long)t * B + bidx) * S + blockIdx.x) * kTrajSums + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
+// metrics = { loss_avg, loss_full, diverged_t, mean_t p, step_loss[n_steps], p[n_steps] }; one workgroup, every sum in index order
+__global__ __launch_bounds__(256) void markov_traj_metrics_kernel(const float* __restrict__ sums, float* metrics, int B, int S,
+                                                                  int n_steps, float threshold) {
+    __shared__ float full[256];
+    const float* row = sums;
+    auto slice_sum = [&](int t, int b, int k) {
+        float a = 0.f;
+        for (int sl = 0; sl < S; ++sl) a += row[(((long)t * B + b) * S + sl) * kTrajSums + k];
+        return a;
+    };
+    for (int t = threadIdx.x; t < n_steps; t += 256) {
+        float l = 0.f, p = 0.f;
+        for (int b = 0; b < B; ++b) {
+            l += sqrtf(slice_sum(t, b, 0)) / sqrtf(slice_sum(t, b, 1));
+            p += slice_sum(t, b, 4) / (sqrtf(slice_sum(t, b, 2)) * sqrtf(slice_sum(t, b, 3)));
+        }
+        metrics[4 + t] = l / (float)B;
+        metrics[4 + n_steps + t] = p / (float)B;
+    }
+    float f = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        float d2 = 0.f, y2 = 0.f;
+        for (int t = 0; t < n_steps; ++t) d2 += slice_sum(t, b, 5), y2 += slice_sum(t, b, 3);
+        f += sqrtf(d2) / sqrtf(y2);
+    }
+    full[threadIdx.x] = f;
+    __syncthreads();      // also orders this workgroup's metrics[4..] stores before thread 0 reads them back
+    if (threadIdx.x == 0) {
+        float lf = 0.f, la = 0.f, pm = 0.f;
+        for (int i = 0; i < min(B, 256); ++i) lf += full[i];
+        int diverged = n_steps;
+        for (int t = n_steps - 1; t >= 0; --t)
+            if (metrics[4 + n_steps + t] < threshold) diverged = t;
+        for (int t = 0; t < n_steps; ++t) la += metrics[4 + t], pm += metrics[4 + n_steps + t];
+        metrics[0] = la / (float)n_steps;
+        metrics[1] = lf / (float)B;
+        metrics[2] = (float)diverged;
+        metrics[3] = pm / (float)n_steps;
+    }
+}
+
 // ---- fused flat AdamW ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
@@ -905,6 +994,32 @@ extern "C" int ffno_markov_features(const float* x, float* state, float* derived
     const unsigned blocks = (unsigned)min((P * D + 255) / 256, 2048L);
     FFNO_LAUNCH(markov_features_kernel, dim3(blocks), dim3(256), 0, s, src, derived, noise, out, P, D, M, N, low, high,
                 noise_std, normalize);
+    return pw_status();
+}
+
+// (the loss kernel's slicing: 1024 elements per slice, at most 64 slices per sample)
+extern "C" size_t ffno_markov_traj_ws_floats(int B, int M, int N, int n_steps) {
+    if (B <= 0 || M <= 0 || N <= 0 || n_steps <= 0 || (long)M * N > 0x7fffffffL) return 0;
+    return (size_t)n_steps * (size_t)B * (size_t)lploss_slices(M * N) * (size_t)kTrajSums;
+}
+
+extern "C" int ffno_markov_traj_step(const float* out, const float* affine, const float* prev, const float* data, float* im,
+                                     float* preds, float* sums, int B, int M, int N, int T, int n_steps, int t, void* stream) {
+    if (!out || !data || !im || !preds || !sums || B <= 0 || M <= 0 || N <= 0) return FFNO_EINVAL;
+    if (n_steps <= 0 || n_steps > T || t < 0 || t >= n_steps) return FFNO_EINVAL;
+    if ((long)M * N > 0x7fffffffL || B > 65535) return FFNO_EUNSUPPORTED;
+    const int n = M * N;
+    FFNO_LAUNCH(markov_traj_step_kernel, dim3(lploss_slices(n), B), dim3(256), 0, (hipStream_t)stream, out, affine, prev, data, im,
+                preds, sums, n, T, n_steps, t);
+    return pw_status();
+}
+
+extern "C" int ffno_markov_traj_metrics(const float* sums, float* metrics, int B, int M, int N, int n_steps, float threshold,
+                                        void* stream) {
+    if (!sums || !metrics || B <= 0 || M <= 0 || N <= 0 || n_steps <= 0) return FFNO_EINVAL;
+    if ((long)M * N > 0x7fffffffL) return FFNO_EUNSUPPORTED;
+    FFNO_LAUNCH(markov_traj_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, metrics, B, lploss_slices(M * N),
+                n_steps, threshold);
     return pw_status();
 }
 

@@ -2,8 +2,8 @@
 ``fourierflow.routines.Grid2DMarkovExperiment`` (reference routines/grid_2d_markov.py:23-193, 374-390)
 without Lightning / wandb / jax: feature build (positional channels, running normaliser, Gaussian noise),
 the operator, inverse-normalise + relative-L2 loss, the manual optimisation step
-(routines/base.py:27-52), epoch-0 statistics accumulation, and the autoregressive rollout of
-``_valid_step`` (:195-326) used by predict/infer.
+(routines/base.py:27-52), epoch-0 statistics accumulation, the autoregressive rollout used by predict/infer, and the
+trajectory validation / test metrics of ``_valid_step`` / ``compute_losses`` / ``validation_step`` / ``test_step`` (:195-416).
 
 Everything on the device is a HIP kernel of libffno_hip.so; torch supplies memory, the stream and the
 Gaussian noise samples.
@@ -30,8 +30,8 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                  use_position: bool = True, append_force: bool = False, append_mu: bool = False,
                  max_accumulations: float = 1e6, should_normalize: bool = True, use_fourier_position: bool = False,
                  noise_std: float = 0.0, shuffle_grid: bool = False, use_velocity: bool = False,
-                 learn_difference: bool = False, optimizer: Optional[dict] = None, scheduler: Optional[dict] = None,
-                 domain=((0.0, 2 * math.pi), (0.0, 2 * math.pi)), grid_size=(64,), **unused):
+                 learn_difference: bool = False, step_size: float = 1.0, optimizer: Optional[dict] = None,
+                 scheduler: Optional[dict] = None, domain=((0.0, 2 * math.pi), (0.0, 2 * math.pi)), grid_size=(64,), **unused):
         super().__init__()
         reject_unsupported_routine_kwargs(unused)
         if use_fourier_position:
@@ -47,6 +47,7 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                 self.register_buffer(f"_{name}_inv", torch.argsort(idx), persistent=False)   # not part of the state_dict
         self.use_position, self.append_force, self.append_mu = bool(use_position), bool(append_force), bool(append_mu)
         self.n_steps, self.low, self.high = n_steps, low, high
+        self.step_size = float(step_size)      # physical time per model step: `time_until` = diverged step * step_size (:348)
         self.should_normalize, self.noise_std, self.learn_difference = should_normalize, noise_std, learn_difference
         self.normalizer = Normalizer([conv.input_dim], max_accumulations)
         self.register_buffer('_float', torch.FloatTensor([0.1]))
@@ -227,3 +228,118 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
             x = im
         self.normalizer.train(was_training)
         return torch.cat(preds, dim=-1)
+
+    # -- trajectory validation (grid_2d_markov.py:195-416) ---------------------------------------------------------------------
+    def _traj_geometry(self, data: torch.Tensor):
+        B, M, N, T = data.shape
+        n_steps = self.n_steps or T - 1
+        if not 0 < n_steps < T:
+            raise ValueError(f"n_steps={n_steps} needs a trajectory of at least {n_steps + 1} steps, batch['data'] has {T}")
+        return B, M, N, T, n_steps
+
+    @torch.no_grad()
+    def _valid_step(self, batch: Dict[str, torch.Tensor]):
+        """Autoregressive rollout over batch['data'] [B, M, N, T] from data[..., T - n_steps - 1] (:195-326) ->
+        (summed step loss, step_losses [n_steps], preds [B, M, N, n_steps], []).  No noise, no statistics accumulation.  Per step:
+        the feature kernel, the inference engine, one ffno_markov_traj_step launch (inverse normalisation, difference
+        update, next input, preds column and the sums of every metric); ffno_markov_traj_metrics after the loop.  The last
+        entry is the reference's `forecast_list` per step, which the inference engine does not produce."""
+        data = batch['data'].contiguous().float()
+        _lib.require_device_tensor(data, "batch['data']")
+        B, M, N, T, n_steps = self._traj_geometry(data)
+        dev, lib, stream = data.device, _lib.get_lib(), _lib.current_stream(data.device)
+        force = batch['f'].float() if self.append_force else None
+        if force is not None and force.dim() == 4:      # [B, M, N, T']: the last n_steps maps, one per step (:245-247)
+            force = force[..., -n_steps:]
+            if force.shape[-1] != n_steps:
+                raise ValueError(f"batch['f'] holds {force.shape[-1]} force maps, the rollout needs {n_steps}")
+        mu = batch['mu'] if self.append_mu else None
+        sums = torch.empty(int(lib.ffno_markov_traj_ws_floats(B, M, N, n_steps)), dtype=torch.float32, device=dev)
+        metrics = torch.empty(4 + 2 * n_steps, dtype=torch.float32, device=dev)
+        preds = torch.empty(B, M, N, n_steps, dtype=torch.float32, device=dev)
+        im = data[..., T - n_steps - 1].unsqueeze(-1).contiguous()      # the first input; then every prediction, in place
+        prev = _p(im) if self.learn_difference else None                 # prev_im is the running field itself (:316-318)
+        tr = self.trainer()
+        was_training = self.normalizer.training
+        self.normalizer.eval()
+        try:
+            affine = None
+            for t in range(n_steps):
+                f_t = force if force is None or force.dim() == 3 else force[..., t].contiguous()
+                feats = self._build_features({'x': im, 'f': f_t, 'mu': mu}, add_noise=False)
+                if t == 0:      # the statistics stand still during validation: one inverse affine for the whole rollout
+                    affine = self._affine_tensor()
+                out = self._unshuffle(tr.engine.forward(self._shuffle(feats), False))
+                if tuple(out.shape) != (B, M, N, 1):
+                    raise ValueError(f"the rollout feeds one predicted channel back, conv returned {tuple(out.shape)}")
+                _capi.check(lib.ffno_markov_traj_step(_p(out), _p(affine), prev, _p(data), _p(im), _p(preds), _p(sums),
+                                                      B, M, N, T, n_steps, t, stream), "markov_traj_step")
+        finally:
+            self.normalizer.train(was_training)
+        _capi.check(lib.ffno_markov_traj_metrics(_p(sums), _p(metrics), B, M, N, n_steps, 0.95, stream), "markov_traj_metrics")
+        self._traj = (preds, metrics)
+        step_losses = metrics[4:4 + n_steps]
+        return step_losses.sum(), step_losses, preds, []
+
+    @torch.no_grad()
+    def compute_losses(self, batch: Dict[str, torch.Tensor], loss, preds: torch.Tensor):
+        """(loss / n_steps, loss_full, time_until, reduced_time_until, p, times) of :328-372.  For the `preds` of the last
+        `_valid_step` everything was reduced on the device already; any other `preds` goes through the same two kernels
+        (their sums 2..5 depend on the predictions alone).  One host read: `self.last_metrics`."""
+        data = batch['data'].contiguous().float()
+        B, M, N, T, n_steps = self._traj_geometry(data)
+        if 'corr_data' in batch and batch['corr_data'].shape[1] != M:
+            raise NotImplementedError("corr_data of another grid size needs downsample_vorticity (jax-cfd), which is not built: "
+                                      "pass corr_data at the model's own resolution")
+        cached = getattr(self, "_traj", None)
+        if cached is not None and cached[0] is preds:
+            metrics = cached[1]
+            loss = metrics[0]
+        else:
+            if tuple(preds.shape) != (B, M, N, n_steps):
+                raise ValueError(f"preds must be {(B, M, N, n_steps)}, got {tuple(preds.shape)}")
+            _lib.require_device_tensor(preds, "preds")
+            lib, stream = _lib.get_lib(), _lib.current_stream(data.device)
+            sums = torch.empty(int(lib.ffno_markov_traj_ws_floats(B, M, N, n_steps)), dtype=torch.float32, device=data.device)
+            metrics = torch.empty(4 + 2 * n_steps, dtype=torch.float32, device=data.device)
+            im, again = torch.empty(B, M, N, dtype=torch.float32, device=data.device), torch.empty_like(preds)
+            for t in range(n_steps):
+                col = preds[..., t].contiguous().float()
+                _capi.check(lib.ffno_markov_traj_step(_p(col), None, None, _p(data), _p(im), _p(again), _p(sums),
+                                                      B, M, N, T, n_steps, t, stream), "markov_traj_step")
+            _capi.check(lib.ffno_markov_traj_metrics(_p(sums), _p(metrics), B, M, N, n_steps, 0.95, stream), "markov_traj_metrics")
+            loss = loss / n_steps
+        host = metrics.cpu()
+        self.last_metrics = host
+        time_until = float(host[2]) * self.step_size
+        times = batch['times'][0, -n_steps:] if 'times' in batch else None
+        # corr_data at the grid's own size: the reduced metrics ARE the full ones (:351-357)
+        return loss, metrics[1], time_until, time_until, metrics[4 + n_steps:], times
+
+    def _trajectory_metrics(self, batch):
+        loss, step_losses, preds, _ = self._valid_step(batch)
+        loss, loss_full, time_until, reduced, p, times = self.compute_losses(batch, loss, preds)
+        return loss, loss_full, time_until, reduced, p, times, step_losses
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        """The reference's logged validation keys (:392-406); a NaN loss becomes 9999.9 so that checkpoint selection by
+        `valid_loss` never prefers a diverged model."""
+        loss, loss_full, time_until, reduced, p, _, _ = self._trajectory_metrics(batch)
+        host = self.last_metrics
+        if math.isnan(float(host[0])):
+            loss = 9999.9
+        if math.isnan(float(host[1])):
+            loss_full = 9999.9
+        return {'valid_loss_avg': loss, 'valid_loss': loss_full, 'valid_time_until': time_until,
+                'valid_reduced_time_until': reduced, 'valid_corr': float(host[3])}
+
+    def test_step(self, batch, batch_idx: int = 0):
+        """The reference's logged test keys (:408-425); its two wandb tables are returned as `test_correlations` (p per step)
+        and `test_losses` (relative-L2 per step), with `test_times` when the batch carries `times`."""
+        loss, loss_full, time_until, reduced, p, times, step_losses = self._trajectory_metrics(batch)
+        out = {'test_loss_avg': loss, 'test_loss': loss_full, 'test_time_until': time_until,
+               'test_reduced_time_until': reduced, 'test_corr': float(self.last_metrics[3]),
+               'test_correlations': p, 'test_losses': step_losses}
+        if times is not None:
+            out['test_times'] = times
+        return out

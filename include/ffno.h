@@ -849,6 +849,32 @@ int ffno_markov_features(const float* x, float* state, float* derived, const flo
                          const ffno_markov_extra* extra, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Trajectory validation of the Markov routine (routines/grid_2d_markov.py:195-372): the glue of one autoregressive step and
+ * every metric of `compute_losses`, fp32, deterministic (fixed slices added in a fixed order, no atomics).
+ *
+ * ffno_markov_traj_step -- one launch per rollout step t.  With yy[t] = data[..., T - n_steps + t] (data [B][M][N][T]):
+ *   raw = affine ? fma(out, affine[0], affine[1]) : out        (affine = the {std[0], mean[0]} pair of ffno_lploss_fwd_bwd)
+ *   P   = prev ? prev + raw : raw                              (prev given = learn_difference)
+ *   y   = prev ? yy[t] - yy[t-1] : yy[t]                       (t = 0: yy[-1] is the LAST step, Python indexing, :309-310)
+ *   im[b][m][n] = preds[b][m][n][t] = P                        (preds [B][M][N][n_steps]; im may be `prev` or `out` itself)
+ *   sums[t][b][slice][0..5] = partial sums over the slice of
+ *     (raw-y)^2, y^2 | P^2, yy[t]^2, P yy[t] | (P-yy[t])^2     (step loss | correlation | trajectory loss)
+ *   sums holds ffno_markov_traj_ws_floats(B, M, N, n_steps) = n_steps B S 6 floats, S = min(64, ceil(M N / 1024)) slices per sample.
+ *
+ * ffno_markov_traj_metrics -- one launch after the loop; s_k = the S partials of sums[t][b][.][k] added in slice order:
+ *   metrics[4 + t]           step_loss[t] = mean_b sqrt(s0) / sqrt(s1)
+ *   metrics[4 + n_steps + t] p[t]         = mean_b s4 / (sqrt(s2) sqrt(s3))
+ *   metrics[0] loss_avg  = sum_t step_loss[t] / n_steps        metrics[1] loss_full = mean_b sqrt(sum_t s5) / sqrt(sum_t s3)
+ *   metrics[2] diverged_t = first t with p[t] < threshold, n_steps if none (as a float)       metrics[3] mean_t p[t]
+ *   metrics holds 4 + 2 n_steps floats: one host read per validation batch.
+ * --------------------------------------------------------------------------------------------- */
+size_t ffno_markov_traj_ws_floats(int B, int M, int N, int n_steps);
+int ffno_markov_traj_step(const float* out, const float* affine, const float* prev, const float* data, float* im,
+                          float* preds, float* sums, int B, int M, int N, int T, int n_steps, int t, void* stream);
+int ffno_markov_traj_metrics(const float* sums, float* metrics, int B, int M, int N, int n_steps, float threshold,
+                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused AdamW over one flat parameter buffer (torch.optim.AdamW semantics, config.yaml:36-40):
  *   p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
  *   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)        with g := grad * grad_scale
