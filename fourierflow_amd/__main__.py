@@ -1,4 +1,4 @@
-"""`python -m fourierflow_amd {train,test,predict} ...` -- see fourierflow_amd/cli.py."""
+"""`python -m fourierflow_amd {train,test,predict,generate} ...` -- see fourierflow_amd/cli.py."""
 from .cli import main
 
 main()

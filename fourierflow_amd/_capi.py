@@ -278,6 +278,10 @@ SIGNATURES = {
     "ffno_pchead_partial_floats": (SZ, [I, I, I, I]),
     "ffno_pchead_fwd": (I, [P, P, P, P, P, I, I, I, I, P]),
     "ffno_pchead_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
+    "ffno_ns2d_supported": (I, [I]),
+    "ffno_ns2d_derivs": (I, [P, P, I, I, P]),
+    "ffno_ns2d_advect": (I, [P, P, SZ, P]),
+    "ffno_ns2d_cn_update": (I, [P, P, P, P, F, I, I, I, P]),
 }
 
 

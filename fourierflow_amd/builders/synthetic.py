@@ -1,0 +1,164 @@
+"""The 2-D Navier-Stokes data generator -- MI355X-native mirror of ``fourierflow.builders.synthetic`` (reference
+builders/synthetic/ns_2d.py, random_fields.py): ``Force``, ``GaussianRF`` and ``solve_navier_stokes_2d`` with the reference's
+signatures and return values.
+
+The solver is the reference's pseudo-spectral Crank-Nicolson scheme (ns_2d.py:126-192) on ``torch.fft.rfft2`` half spectra.  Per
+step: ``ffno_ns2d_derivs`` (the spectra of q, v, w_x, w_y from one read of w_h), one batched ``irfft2`` of the four,
+``ffno_ns2d_advect`` (q w_x + v w_y), one ``rfft2``, ``ffno_ns2d_cn_update`` (dealias, force, update of w_h in place) -- three HIP
+launches (csrc/ffno_ns2d.h) around two real rocFFT transforms, where the reference runs about forty element-wise launches around
+five complex ones.  ``GaussianRF`` runs once per batch and stays plain torch, as in the reference.  HIP only: CPU tensors raise
+(the tests route them through the emulator build of the same kernels).
+"""
+from __future__ import annotations
+
+import math
+from enum import Enum
+
+import numpy as np
+import torch
+
+from .. import _capi, _lib
+from ..engine import _p
+
+
+class Force(str, Enum):
+    li = 'li'
+    random = 'random'
+    none = 'none'
+    kolmogorov = 'kolmogorov'
+
+
+class GaussianRF:
+    """Gaussian random field on the periodic unit square with covariance sigma^2 (-lap + tau^2)^(-alpha) (the 2-D case of the
+    reference's random_fields.py): ``sample(n)`` -> [n, size, size], float32 on ``device``.
+
+    Mode k of a sample is a complex standard normal times  size^2 sqrt(2) sigma (4 pi^2 |k|^2 + tau^2)^(-alpha / 2); the mean mode
+    is left out and the field is the real part of the inverse transform.  sigma defaults to tau^(alpha - 1)."""
+
+    def __init__(self, n_dims, size, alpha=2, tau=3, sigma=None, device=None):
+        if n_dims != 2:
+            raise NotImplementedError(f"GaussianRF: n_dims={n_dims}; only the 2-D field of `generate navier-stokes` is built")
+        self.n_dims, self.size, self.device = 2, int(size), device
+        if sigma is None:
+            sigma = tau ** (alpha - 1.0)
+        i = torch.arange(self.size, device=device)
+        k = torch.where(i < self.size // 2, i, i - self.size).float()           # 0 .. size/2-1, -size/2 .. -1
+        k2 = k[:, None] ** 2 + k[None, :] ** 2
+        self.amplitude = self.size ** 2 * math.sqrt(2.0) * sigma * (4 * math.pi ** 2 * k2 + tau ** 2) ** (-0.5 * alpha)
+        self.amplitude[0, 0] = 0.0
+
+    def sample(self, n):
+        # ONE normal draw of [n, size, size, 2], (real, imaginary) innermost: the order that ties the fields to the torch seed
+        noise = torch.randn(n, self.size, self.size, 2, device=self.device)
+        return torch.fft.ifft2(self.amplitude * torch.view_as_complex(noise)).real
+
+
+def _unit_grid(N, device):
+    """(X, Y), each [N, N]: the grid points i / N of the unit square, X along axis 0 and Y along axis 1."""
+    g = torch.arange(N, dtype=torch.float32, device=device) / N
+    return g[:, None].expand(N, N), g[None, :].expand(N, N)
+
+
+def random_force(B, N, device, cycles, scaling, seed):
+    """[B, N, N]: per sample, ``scaling`` times the sum over p = 1 .. cycles of sin and cos of 2 pi p x, 2 pi p y and
+    2 pi p (x + y), each with its own uniform amplitude.  The amplitudes come from a generator on ``device`` seeded with ``seed``,
+    one draw of B per term in the order (p; x, y, x + y; sin, cos) -- the order of the reference's get_random_force, so that a
+    seed gives the same force."""
+    gen = torch.Generator(device)
+    gen.manual_seed(seed)
+    X, Y = _unit_grid(N, device)
+    f = torch.zeros(B, N, N, device=device)
+    for p in range(1, cycles + 1):
+        for phase in (X, Y, X + Y):
+            for wave in (torch.sin, torch.cos):
+                amplitude = torch.rand(B, 1, 1, generator=gen, device=device)
+                f += amplitude * wave(2 * math.pi * p * phase)
+    return scaling * f
+
+
+def _force_field(force, B, N, device, cycles, scaling, seed):
+    """li: 0.1 (sin + cos)(2 pi (x + y)), [N, N]; kolmogorov: -4 cos(4 . 2 pi y), [N, N]; random: [B, N, N]; none: None."""
+    if force == Force.none:
+        return None
+    if force == Force.random:
+        return random_force(B, N, device, cycles, scaling, seed)
+    X, Y = _unit_grid(N, device)
+    if force == Force.kolmogorov:
+        return -4 * torch.cos(8 * math.pi * Y)
+    phase = 2 * math.pi * (X + Y)
+    return 0.1 * (torch.sin(phase) + torch.cos(phase))
+
+
+class SpectralStepper:
+    """The state of one batch between steps: w_h, the half spectrum [B, N, N/2+1, 2] of the vorticity, advanced in place by
+    ``step()`` (ns_2d.py:126-175): derivs -> irfft2 of the four spectra -> advect -> rfft2 -> cn_update."""
+
+    def __init__(self, w0, nu, f, delta_t):
+        self.lib = _lib.get_lib()
+        self.B, self.N = int(w0.shape[0]), int(w0.shape[-1])
+        dev = w0.device
+        self.nu, self.delta_t = nu.contiguous(), float(delta_t)
+        self.f_h = None if f is None else torch.view_as_real(torch.fft.rfft2(f.float())).contiguous()
+        self.f_batched = int(self.f_h is not None and self.f_h.dim() == 4)
+        self.w_h = torch.view_as_real(torch.fft.rfft2(w0.contiguous())).contiguous()
+        self.spec4 = torch.empty(4, self.B, self.N, self.N // 2 + 1, 2, dtype=torch.float32, device=dev)
+        self.adv = torch.empty(self.B, self.N, self.N, dtype=torch.float32, device=dev)
+
+    def step(self):
+        lib, B, N = self.lib, self.B, self.N
+        st = _lib.current_stream(self.w_h.device)      # read per step: the transforms in between run on torch's current stream
+        _capi.check(lib.ffno_ns2d_derivs(_p(self.w_h), _p(self.spec4), B, N, st), "ns2d_derivs")
+        fields = torch.fft.irfft2(torch.view_as_complex(self.spec4), s=(N, N)).contiguous()      # q, v, w_x, w_y [4, B, N, N]
+        _capi.check(lib.ffno_ns2d_advect(_p(fields), _p(self.adv), self.adv.numel(), st), "ns2d_advect")
+        F_h = torch.view_as_real(torch.fft.rfft2(self.adv)).contiguous()
+        _capi.check(lib.ffno_ns2d_cn_update(_p(self.w_h), _p(F_h), _p(self.f_h), _p(self.nu), self.delta_t, self.f_batched, B, N, st),
+                    "ns2d_cn_update")
+
+    def vorticity(self):
+        return torch.fft.irfft2(torch.view_as_complex(self.w_h), s=(self.N, self.N))
+
+
+def solve_navier_stokes_2d(w0, visc, T, delta_t, record_steps, cycles=None, scaling=None, t_scaling=None, force=Force.li,
+                           varying_force=False):
+    """Solve the 2-D Navier-Stokes equations in vorticity form with the Crank-Nicolson method (reference ns_2d.py:23-200).
+
+    w0: initial vorticity [B, N, N] (float32, on the GPU; N a power of two, 8 ... 512); visc: viscosity, a float or a numpy
+    array [B]; T: final time; delta_t: internal time step; record_steps: number of snapshots.
+    Returns ``(sol, f)``: sol [B, N, N, record_steps] (numpy) and the force field (numpy; None for ``Force.none``).
+    """
+    seed = np.random.randint(1, 1000000000)      # drawn whatever the force is, like the reference (:46): same numpy stream
+    force = Force(force)
+    if varying_force:
+        raise NotImplementedError("solve_navier_stokes_2d: varying_force (a new random force at every step, ns_2d.py:167-170) "
+                                  "is not built")
+    _lib.require_device_tensor(w0, "w0")
+    if w0.dim() != 3 or w0.shape[1] != w0.shape[2]:
+        raise ValueError(f"w0: expected [B, N, N], got {tuple(w0.shape)}")
+    lib = _lib.get_lib()
+    B, N = int(w0.shape[0]), int(w0.shape[-1])
+    if not lib.ffno_ns2d_supported(N):
+        raise ValueError(f"solve_navier_stokes_2d: grid size {N} is not a power of two in 8 ... 512 (ffno_ns2d_supported)")
+    dev = w0.device
+    steps = math.ceil(T / delta_t)
+    record_time = math.floor(steps / record_steps)
+    if record_time < 1:
+        raise ValueError(f"{steps} solver steps cannot give {record_steps} snapshots")
+
+    if isinstance(visc, np.ndarray):
+        if visc.shape != (B,):
+            raise ValueError(f"visc: expected a float or an array of shape ({B},), got {visc.shape}")
+        nu = torch.from_numpy(np.ascontiguousarray(visc, dtype=np.float32)).to(dev)
+    else:
+        nu = torch.full((B,), float(visc), dtype=torch.float32, device=dev)
+
+    f = _force_field(force, B, N, dev, cycles, scaling, seed)
+    stepper = SpectralStepper(w0, nu, f, delta_t)
+    snapshots = []
+    for _ in range(record_steps):      # a snapshot after every record_time steps; steps past the last snapshot change nothing
+        for _ in range(record_time):
+            stepper.step()
+        w = stepper.vorticity()
+        if bool(torch.isnan(w).any()):
+            raise ValueError(f"solve_navier_stokes_2d: NaN in snapshot {len(snapshots) + 1} of {record_steps}")
+        snapshots.append(w)
+    return torch.stack(snapshots, dim=-1).cpu().numpy(), (None if f is None else f.cpu().numpy())

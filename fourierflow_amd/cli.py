@@ -1,4 +1,5 @@
-"""`python -m fourierflow_amd {train,test,predict} CONFIG.yaml [overrides...]` -- the command surface of the reference
+"""`python -m fourierflow_amd {train,test,predict} CONFIG.yaml [overrides...]` and `python -m fourierflow_amd generate
+navier-stokes PATH` (the data the 2-D Navier-Stokes configs train on, see `navier_stokes` below) -- the command surface of the reference
 (`fourierflow train | test | predict`, reference commands/train.py:27-148, commands/test.py:24-90,
 commands/predict.py:24-110) for the routines built here, with the same positional arguments and flag names
 (``--force --resume --checkpoint-id --trial --debug --no-logging --map-location``) and the same on-disk layout:
@@ -27,6 +28,7 @@ import numpy as np
 import torch
 from typer import Argument, Option, Typer
 
+from .builders.synthetic import Force
 from .config import build_routine, load_config
 
 app = Typer(add_completion=False, help=__doc__)
@@ -367,6 +369,133 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     np.savez(str(out), preds=preds.detach().cpu().numpy())
     print(json.dumps(dict(checkpoint=str(ckpt), predictions=str(out), shape=list(preds.shape),
                           inference_time_ms_per_step=round(1e3 * elapsed / steps, 4))), flush=True)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+generate_app = Typer(add_completion=False, help="Generate datasets on the GPU.")
+app.add_typer(generate_app, name="generate")
+
+
+@generate_app.callback()
+def _generate():
+    """Generate datasets on the GPU (the reference's `fourierflow generate`, commands/generate.py)."""
+
+
+def _training_pairs(u: np.ndarray):
+    """u [n, M, N, T] -> x, y [(n (T - 1)), M, N, 1]: every snapshot with its successor, sample-major -- the (b t) order in which
+    the reference's NavierStokesTrainingDataset enumerates its pairs (builders/ns_contextual.py:57-72 with k = 1)."""
+    n, M, N, T = u.shape
+    x = np.ascontiguousarray(np.moveaxis(u[..., :-1], -1, 1)).reshape(n * (T - 1), M, N, 1)
+    y = np.ascontiguousarray(np.moveaxis(u[..., 1:], -1, 1)).reshape(n * (T - 1), M, N, 1)
+    return x, y
+
+
+class _NpzStream:
+    """An .npz file whose arrays are filled some rows at a time, so that host memory holds one batch and not the split: every
+    array is a memory-mapped .npy file in a scratch directory beside the output, and ``close()`` packs them, stored and not
+    compressed like ``np.savez``, into the .npz and returns their shapes."""
+
+    def __init__(self, out: str, rows: int):
+        import os
+        import tempfile
+        self.out, self.rows, self.arrays = out, rows, {}
+        self.scratch = tempfile.mkdtemp(prefix=os.path.basename(out) + ".", dir=os.path.dirname(out) or ".")
+
+    def put(self, name: str, row: int, block: np.ndarray):
+        import os
+        if name not in self.arrays:
+            self.arrays[name] = np.lib.format.open_memmap(os.path.join(self.scratch, name + ".npy"), mode="w+", dtype=np.float32,
+                                                          shape=(self.rows, *block.shape[1:]))
+        self.arrays[name][row:row + len(block)] = block
+
+    def close(self) -> Dict[str, List[int]]:
+        import os
+        import shutil
+        import zipfile
+        shapes = {name: list(a.shape) for name, a in self.arrays.items()}
+        for a in self.arrays.values():
+            a.flush()
+        self.arrays.clear()
+        with zipfile.ZipFile(self.out, "w", zipfile.ZIP_STORED, allowZip64=True) as z:
+            for name in shapes:
+                z.write(os.path.join(self.scratch, name + ".npy"), name + ".npy")
+        shutil.rmtree(self.scratch)
+        return shapes
+
+
+@generate_app.command("navier-stokes")
+def navier_stokes(path: str = Argument(..., help="prefix of the files to write: PATH.train.npz, PATH.valid.npz, PATH.test.npz"),
+                  n_train: int = Option(1000, help="trajectories in PATH.train.npz"),
+                  n_valid: int = Option(200, help="trajectories in PATH.valid.npz"),
+                  n_test: int = Option(200, help="trajectories in PATH.test.npz"),
+                  s: int = Option(256, help="grid points per side (a power of two, 8 ... 512)"),
+                  t: float = Option(20, help="time the flow is integrated to"),
+                  steps: int = Option(20, help="snapshots kept per trajectory, evenly spaced up to --t"),
+                  mu: float = Option(1e-5, help="viscosity of every trajectory when --mu-min equals --mu-max"),
+                  mu_min: float = Option(1e-5, help="lower end of the per-trajectory uniform viscosity"),
+                  mu_max: float = Option(1e-5, help="upper end of the per-trajectory uniform viscosity"),
+                  seed: int = Option(23893, help="seeds torch (initial vorticity) and, plus 1234, numpy (viscosity, force)"),
+                  delta: float = Option(1e-4, help="time step of the solver"),
+                  batch_size: int = Option(50, help="trajectories solved at once"),
+                  force: Force = Option(Force.li.value, help="forcing term of the vorticity equation"),
+                  cycles: int = Option(2, help="--force random: harmonics per direction"),
+                  scaling: float = Option(0.1, help="--force random: factor on the summed harmonics"),
+                  ssr: int = Option(1, help="keep every ssr-th grid point of the solutions (the builders' stride subsampling)"),
+                  device: Optional[str] = Option(None, hidden=True)):
+    """Generate 2-D Navier-Stokes trajectories (the reference's `fourierflow generate navier-stokes`: GaussianRF initial vorticity,
+    the Crank-Nicolson solver, the same options and seeding) and write them as the .npz files `train` / `test` / `predict` read:
+    PATH.train.npz holds x / y pairs [, f, mu], PATH.valid.npz and PATH.test.npz whole trajectories data [n, M, N, T], times
+    [, f, mu].  `f` is written for --force random, `mu` when --mu-min and --mu-max differ.  Each split is solved --batch-size
+    trajectories at a time, with a shorter last batch where that does not divide the split, and written batch by batch."""
+    import os
+
+    from typer import BadParameter
+
+    from .builders.synthetic import GaussianRF, solve_navier_stokes_2d
+    if steps < 2:
+        raise BadParameter("a training pair needs two snapshots", param_hint="--steps")
+    if batch_size < 1 or ssr < 1:
+        raise BadParameter("--batch-size and --ssr are at least 1")
+    dev = _device(device)
+    torch.manual_seed(seed)
+    np.random.seed(seed + 1234)
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    field = GaussianRF(2, s, alpha=2.5, tau=7, device=dev)
+    n_solver = math.ceil(t / delta)
+    times = (np.arange(1, steps + 1) * (n_solver // steps) * delta).astype(np.float32)
+    vary_mu, pairs = mu_min != mu_max, steps - 1
+    written = {}
+    for split, n in (("train", n_train), ("valid", n_valid), ("test", n_test)):
+        if n <= 0:
+            continue
+        rows_per_sample = pairs if split == "train" else 1      # the per-sample f and mu are repeated for every pair
+        sink = _NpzStream(f"{path}.{split}.npz", n * rows_per_sample)
+        done = 0
+        while done < n:
+            b = min(batch_size, n - done)
+            # per batch, in this order: the initial vorticity from torch's generator; the viscosities, then (inside the solver)
+            # the seed of the random force from numpy's
+            with torch.no_grad():
+                w0 = field.sample(b)
+            nu = mu_min + (mu_max - mu_min) * np.random.rand(b) if vary_mu else mu
+            sol, f = solve_navier_stokes_2d(w0, nu, t, delta, steps, cycles, scaling, None, force, False)
+            sol = sol[:, ::ssr, ::ssr]
+            row = done * rows_per_sample
+            if split == "train":
+                x, y = _training_pairs(sol)
+                sink.put("x", row, x)
+                sink.put("y", row, y)
+            else:
+                sink.put("data", row, sol)
+                sink.put("times", row, np.tile(times, (b, 1)))
+            if force == Force.random:
+                sink.put("f", row, np.repeat(f[:, ::ssr, ::ssr], rows_per_sample, axis=0))
+            if vary_mu:
+                sink.put("mu", row, np.repeat(nu, rows_per_sample))
+            done += b
+        written[split] = dict(file=sink.out, trajectories=n, **sink.close())
+    print(json.dumps(dict(solver_steps=n_solver, delta=delta, grid=s, ssr=ssr, **written)), flush=True)
 
 
 def main():

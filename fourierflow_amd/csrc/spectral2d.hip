@@ -289,3 +289,5 @@ extern "C" int ffno_fw3d_grad_reduce(const float* partial, float* g1, float* g2,
 // ... and so do its two per-point networks: IPhi (ffno_iphi_*) and the output head (ffno_pchead_*)
 #include "ffno_iphi.h"
 #include "ffno_pchead.h"
+// the streaming kernels of the Navier-Stokes data generator's solver step (entry points ffno_ns2d_*)
+#include "ffno_ns2d.h"

@@ -1025,6 +1025,34 @@ int ffno_pchead_bwd(const ffno_pchead_params* params, const ffno_pchead_params* 
                     const float* dy, const float* pre, float* dt, float* partial, int B, int N, int W, int out_channels,
                     void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The step of the pseudo-spectral Crank-Nicolson solver behind `generate navier-stokes` (reference
+ * fourierflow/builders/synthetic/ns_2d.py:126-175), fp32, on torch.fft.rfft2 half spectra s[B][N][N/2+1][2].  N a power of two,
+ * 8 <= N <= 512 (ffno_ns2d_supported); B N (N/2+1) < 2^31; every tensor 16-byte aligned (FFNO_EINVAL otherwise).  Wavenumbers
+ * come from the indices: row r is k_x = r (r < N/2) or r - N, column c is k_y = c;  lap = 4 pi^2 (k_x^2 + k_y^2), lap[0][0] = 1
+ * (ns_2d.py:91-101).  Per step the host runs  derivs -> irfft2 of out4 -> advect -> rfft2 -> cn_update;  the FFTs are the
+ * caller's (rocFFT).
+ *   ffno_ns2d_derivs: out4[4][B][N][N/2+1][2] = the spectra of
+ *         q = i 2 pi k_y w_h / lap (ns_2d.py:128-135),  v = -i 2 pi k_x w_h / lap (:137-142),
+ *         w_x = i 2 pi k_x w_h (:144-149),              w_y = i 2 pi k_y w_h (:151-156).
+ *       The reference transforms the full spectrum and keeps `.real`, which drops the anti-Hermitian Nyquist bins of a
+ *       derivative; irfft2 would keep the row k_x = -N/2.  So row N/2 of v and w_x and column N/2 of q and w_y are written as
+ *       zeros, and irfft2 of out4 equals the reference's four fields.
+ *   ffno_ns2d_advect: out[i] = q[i] w_x[i] + v[i] w_y[i] over the four real fields fields4[4][n], n = B N N (a multiple of 4):
+ *       the product of ns_2d.py:159.
+ *   ffno_ns2d_cn_update: w_h in place (ns_2d.py:163, 173-175; F_h is only read):
+ *         w_h = (-dt dealias F_h + dt f_h + (1 - factor) w_h) / (1 + factor),   factor = 0.5 dt visc[b] lap,
+ *       dealias = 1 where |k_x|, |k_y| <= (2/3)(N/2) (:109-113; 3 |k| <= N), else 0.  f_h: NULL (Force.none), one spectrum
+ *       [N][N/2+1][2] for every sample (f_batched = 0) or [B][N][N/2+1][2] (f_batched = 1).  visc[B] on the device (a scalar
+ *       viscosity is expanded by the host, :103-106).
+ * Deterministic; no atomics, no workspace.
+ * --------------------------------------------------------------------------------------------- */
+int ffno_ns2d_supported(int N);
+int ffno_ns2d_derivs(const float* w_h, float* out4, int B, int N, void* stream);
+int ffno_ns2d_advect(const float* fields4, float* out, size_t n, void* stream);
+int ffno_ns2d_cn_update(float* w_h, const float* F_h, const float* f_h, const float* visc, float delta_t, int f_batched, int B,
+                        int N, void* stream);
+
 /* small utilities used by the host driver */
 int ffno_axpy(float* y, const float* x, float alpha, size_t n, void* stream); /* y += alpha*x */
 
