@@ -102,6 +102,22 @@ def current_stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+_twiddles = {}
+
+
+def twiddle(L: int, device):
+    """The device copy of the kernels' length-L twiddle table (L cosines, then L sines, each / sqrt(L)), made once per
+    (L, device, backend)."""
+    key = (L, device, _test_backend is not None)
+    if key not in _twiddles:
+        import numpy as np
+        import torch
+        host = np.zeros(2 * L, np.float32)
+        _capi.check(get_lib().ffno_twiddle_fill_host(host.ctypes.data_as(ctypes.c_void_p), L), "twiddle")
+        _twiddles[key] = torch.from_numpy(host).to(device)
+    return _twiddles[key]
+
+
 def require_device_tensor(t, what: str):
     import torch
     if _test_backend is not None:

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _capi, _lib
+from ._corner_chain import CornerChain
 
 MODES = {"full": 0, "low-pass": 1, "no-fourier": 2}
 HEAD_DIM = 128  # grid_2d.py:150-152 / mesh_3d.py:155-157: WNLinear(width, 128) -> WNLinear(128, out)
@@ -102,13 +103,14 @@ class _Linear:
 
 class _View:
     """One spatial axis as a [Bv, Mv, Nv, C] view: a01 = 0 transforms along Nv, 1 along Mv."""
-    __slots__ = ("Bv", "Mv", "Nv", "a01", "L", "K", "R", "spec", "K2", "spec_y", "x3fmt")
+    __slots__ = ("Bv", "Mv", "Nv", "a01", "L", "K", "R", "spec", "modes", "x3fmt")
 
     def __init__(self, Bv, Mv, Nv, a01, K, C):
         self.Bv, self.Mv, self.Nv, self.a01, self.K = Bv, Mv, Nv, a01, K
         self.L = Nv if a01 == 0 else Mv
         self.R = Bv * Mv if a01 == 0 else Bv * Nv
         self.spec = K * self.R * 2 * C
+        self.modes = K      # what the mix and the weight gradient run over
 
 
 class FFNOEngine:
@@ -588,23 +590,18 @@ class FFNOEngine:
         return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
 
     def _twiddle(self, L: int) -> torch.Tensor:
-        if L not in self._tw:
-            host = np.zeros(2 * L, np.float32)
-            _capi.check(_lib.get_lib().ffno_twiddle_fill_host(host.ctypes.data_as(ctypes.c_void_p), L), "twiddle")
-            self._tw[L] = torch.from_numpy(host).to(self.device)
-        return self._tw[L]
+        tw = self._tw.get(L)       # (this engine's memo of the package's one table cache: asked once per branch launch)
+        if tw is None:
+            tw = self._tw[L] = _lib.twiddle(L, self.device)
+        return tw
 
     # ------------------------------------------------------------------------------------------------
     def _views(self, B: int, Sp: Sequence[int]) -> List[_View]:
         """views[w] = the axis mixed by fourier_weight[w], as a [Bv, Mv, Nv, C] view of the (padded) buffer."""
         C = self.C
         if self.spectral == "plus":
-            M, N = Sp
-            v = _View(B, M, N, 0, self.K, C)          # geometry of the last-axis transforms
-            v.R, v.K2 = B, 2 * self.K * self.K         # rows per mode = samples; retained (ky, kx') modes
-            v.spec_y = v.spec                          # y-transformed spectrum [K][B*M][2][C]
-            v.spec = v.K2 * B * 2 * C                  # 2-D spectrum [K2][B][2][C] (what is saved for the weight gradient)
-            return [v]
+            # one joint (ky, kx') mode set: the chain (ws.chain) stands in for the view (rows per mode = samples, spec = 2-D spectrum)
+            return [CornerChain(B, Sp, (self.K, self.K), C, lambda *a: self._k(*a), self.device)]
         if self.nd == 2:
             M, N = Sp
             if self.first_axis_first:      # mesh_2d.py:71-75,92-96: weight 0 <-> x (first axis), weight 1 <-> y (last axis)
@@ -663,9 +660,8 @@ class FFNOEngine:
             if save:
                 ws.G1 = torch.empty(P, C, **act)                      # ... and of the second adjoint branch
         if self.spectral == "plus":
-            ws.SYa = torch.empty(ws.views[0].spec_y, **f32)           # last-axis spectra on either side of the x transform
-            ws.SYb = torch.empty(ws.views[0].spec_y, **f32)
-            ws.CW = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, self.K, self.K)), **f32)   # first-axis DFT scratch
+            ws.chain = ws.views[0]
+            ws.scr = ws.chain.scratch(lambda n: torch.empty(n, **f32))
         ws.mask_words = int(lib.ffno_ff_mask_words(P, H))
         # range words, one per (tensor kind, layer): x = layer inputs, s = spectral-branch outputs (feed-forward inputs),
         # g = running gradient (both buffers), d = feed-forward data gradients, t / f = LayerNorm / fork-head gradients
@@ -733,8 +729,7 @@ class FFNOEngine:
             ws.nsplit_fw = [max(1, min(max(1, FW_GRAD_WGS // v.K), (L * v.R + 63) // 64)) for v in ws.views]
             if self.spectral == "plus":
                 ws.nsplit_fw = [1]
-            ws.fwpart = [[torch.empty(ws.nsplit_fw[w] * 2 * (ws.views[w].K2 if self.spectral == "plus" else ws.views[w].K)
-                                      * C * C, **f32) for w in range(nv)]
+            ws.fwpart = [[torch.empty(ws.nsplit_fw[w] * 2 * ws.views[w].modes * C * C, **f32) for w in range(nv)]
                          for _ in range(max(len(self._fw_sets), 1))]
             ws.nsplit_lift = max(1, min(1024, (P_in + 127) // 128))     # all slices co-resident (16 KB LDS per workgroup)
             ws.liftpart = torch.empty(ws.nsplit_lift * C * (self.Cin + 1), **f32)
@@ -1108,30 +1103,18 @@ class FFNOEngine:
             br = self._branch(v, src, dst, resid, save, planes, accumulate, True, fwd, rin, rout)
             self._k(name, lib.ffno_spectral_x3, ctypes.byref(br), C, ck_f, ck_i, conj, st)
             return
-        tw = self._twiddle(v.L)
-        if self.spectral == "plus":
-            # rfft2 = last-axis DFT (K bins) then complex DFT along the first axis (2K retained rows); corner mix with the
-            # (ky, kx') pairs as modes and the samples as rows; zero-padded inverse in the opposite order.  The adjoint
-            # is the same chain with the c_k / conjugate flags swapped (cdft_rows(inverse) is the adjoint of the forward).
-            z = save if save is not None else ws.SD
-            self._k("dft_fwd", lib.ffno_dft_fwd, _p(src), _p(ws.SYa), _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, 0, ck_f, st)
-            twm = self._twiddle(v.Mv)
-            self._k("cdft_rows", lib.ffno_cdft_rows_mfma, _p(ws.SYa), _p(z), _p(ws.CW), _p(twm), v.Bv, v.Mv, C, v.K, v.K, 0, st)
-            self._k("mode_mix", lib.ffno_mode_mix, _p(z), _p(planes), _p(ws.SY), v.Bv, C, v.K2, conj, st)
-            self._k("cdft_rows", lib.ffno_cdft_rows_mfma, _p(ws.SY), _p(ws.SYb), _p(ws.CW), _p(twm), v.Bv, v.Mv, C, v.K, v.K, 1,
-                    st)
-            self._k("dft_inv", lib.ffno_dft_inv, _p(ws.SYb), _p(dst), resid, _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, 0, ck_i,
-                    accumulate, st)
+        if self.spectral == "plus":         # (v is ws.chain: the operator's one "view" is the corner chain)
+            ws.chain.conv(src, dst, save if save is not None else ws.SD, ws.SY, planes, ws.scr, fwd, st, resid, accumulate)
         elif self.spectral == "dct":       # DCT branch: the same transform pair serves the forward and the adjoint (orthonormal)
             spec = save if save is not None else ws.SD
             self._k("dct_branch" + ("" if fwd else "(adj)"), lib.ffno_dct_branch, _p(src), _p(dst), resid, _p(spec), _p(ws.SY),
                     _p(planes), _p(self._twiddle(2 * v.L)), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, conj, accumulate, st)
         elif fused:      # (records its output maximum itself)
-            self._k(name, lib.ffno_spectral_fused, _p(src), _p(dst), resid, _p(save), _p(planes), _p(tw),
+            self._k(name, lib.ffno_spectral_fused, _p(src), _p(dst), resid, _p(save), _p(planes), _p(self._twiddle(v.L)),
                     v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_f, ck_i, conj, accumulate, rout, st)
             return
         else:
-            spec = save if save is not None else ws.SD
+            spec, tw = save if save is not None else ws.SD, self._twiddle(v.L)
             self._k("dft_fwd", lib.ffno_dft_fwd, _p(src), _p(spec), _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, v.a01, ck_f, st)
             y = spec
             if planes is not None:
@@ -1654,9 +1637,7 @@ class FFNOEngine:
             l0_, nl = layers[0], len(layers)
             assert layers == list(range(l0_, l0_ + nl))
             if self.spectral == "plus":
-                v = ws.views[0]
-                self._k("fw_grad_partial", lib.ffno_fw_grad_partial, _p(ws.SXall[0][l0_]), _p(ws.SDall[0][l0_]),
-                        _p(ws.fwpart[si][0]), v.R, C, v.K2, ws.nsplit_fw[0], 0, nl, v.spec, v.spec, st)
+                ws.chain.fw_grad_partial(ws.SXall[0][l0_], ws.SDall[0][l0_], ws.fwpart[si][0], st, ws.nsplit_fw[0], nl)
                 self._k("fw2d_grad_reduce", lib.ffno_fw2d_grad_reduce, _p(ws.fwpart[si][0]), _p(gv(names[0])),
                         _p(gv(names[1])), C, self.K, ws.nsplit_fw[0], 0, st)
                 continue

@@ -7,14 +7,13 @@ experiments/{airfoil,pipe,plasticity}/geo-fno*).  2-D:
     -> crop -> fc1 (width -> 128) -> GELU -> fc2 (128 -> 1)
 
 Everything is the kernel set of the FNOZongyi2DBlock path (engine_zongyi.py): the spectral convolution is the
-dft_fwd -> cdft_rows2 -> mode_mix -> cdft_rows2^-1 -> dft_inv chain with separate row / column mode counts, the pointwise
+corner chain of _corner_chain.py with one mode count per axis, the pointwise
 parts are plin.hip with the exact GELU (the pre-activation of every layer is kept for its derivative), fc0 writes
 straight into the padded buffer through the pad map of the F-FNO lift kernel.  width 32 or 64 = the channel tiles of the
 spectral kernels (narrower widths are zero-padded like the Zongyi baseline).
 
 3-D (FNOMesh3D): the same with rfftn over three axes, FOUR corner blocks (+-x, +-y, low z), padding 5, a 1x1x1 convolution and
-four output channels: the z transform is ffno_dft_fwd, the y and x transforms two passes of ffno_cdft_rows_mfma (lines
-(kz, b, x) then ((kz, ky'), b)), the mix runs over the K3 * 2K2 * 2K1 retained modes with the B samples as rows.
+four output channels, on the three-axis form of the same chain.
 """
 from __future__ import annotations
 
@@ -24,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _capi, _lib
-from .engine import _p, _View
+from ._corner_chain import CornerChain
+from .engine import _p
 from .engine_zongyi import HEAD_DIM, ZongyiEngine
 
 ACT_NONE, ACT_GELU = 0, 2
@@ -46,60 +46,25 @@ class GeoFNO2DEngine(ZongyiEngine):
         self.O = 1 if self.nd == 2 else 4             # fc2: 128 -> 1 (mesh_2d.py:76) / 128 -> 4 (mesh_3d.py:84)
         self.nw = 2 if self.nd == 2 else 4            # corner-block weight tensors per layer
         self.Ktot = 2 * modes1 * modes2 * (1 if self.nd == 2 else 2 * modes3)     # retained modes
-        W = width
-        self.param_names, self.param_shapes, self._pad_geom = [], {}, {}
-
-        def add(name, shape, geom):
-            self.param_names.append(name)
-            self.param_shapes[name] = tuple(shape)
-            self._pad_geom[name] = geom      # (R, Cc, inner) of the plain tensor, (Rp, Cp) of its padded twin
-
+        W, O = width, self.O
         # reference registration order: fc0, convs (weights1, weights2 per layer), ws (weight, bias per layer), fc1, fc2
-        add("fc0.weight", (W, input_dim), (W, input_dim, 1, C, input_dim))
-        add("fc0.bias", (W,), (1, W, 1, 1, C))
+        params = [("fc0.weight", (W, input_dim), (W, input_dim, 1, C, input_dim)),
+                  ("fc0.bias", (W,), (1, W, 1, 1, C))]
         mshape = (modes1, modes2) if self.nd == 2 else (modes1, modes2, modes3)
+        for l in range(n_layers):     # complex [I, O, *modes] seen through view_as_real
+            params += [(f"convs.{l}.weights{j}", (W, W, *mshape, 2), (W, W, int(np.prod(mshape)) * 2, C, C))
+                       for j in range(1, self.nw + 1)]
         for l in range(n_layers):
-            for j in range(1, self.nw + 1):     # complex [I, O, *modes] seen through view_as_real
-                add(f"convs.{l}.weights{j}", (W, W, *mshape, 2), (W, W, int(np.prod(mshape)) * 2, C, C))
-        for l in range(n_layers):
-            add(f"ws.{l}.weight", (W, W) + (1,) * self.nd, (W, W, 1, C, C))       # nn.Conv2d / nn.Conv3d(width, width, 1)
-            add(f"ws.{l}.bias", (W,), (1, W, 1, 1, C))
-        add("fc1.weight", (HEAD_DIM, W), (HEAD_DIM, W, 1, HEAD_DIM, C))
-        add("fc1.bias", (HEAD_DIM,), (1, HEAD_DIM, 1, 1, HEAD_DIM))
-        add("fc2.weight", (self.O, HEAD_DIM), (self.O, HEAD_DIM, 1, self.O, HEAD_DIM))
-        add("fc2.bias", (self.O,), (1, self.O, 1, 1, self.O))
-        self._offsets, off, self._poffsets, poff = {}, 0, {}, 0
-        for n in self.param_names:
-            self._offsets[n] = off
-            off += int(np.prod(self.param_shapes[n]))
-            R, Cc, inner, Rp, Cp = self._pad_geom[n]
-            self._poffsets[n] = poff
-            poff += Rp * Cp * inner
-        self.n_params, self.n_padded = off, poff
-        self.params = {}
-        self.device = None
-        self.timer = None
-        self._issue_stream = 0
-        self.paired_last = False
-        self._ws, self._tw = {}, {}
-        self._ptr_sig = None
-        self._packed = False
+            params += [(f"ws.{l}.weight", (W, W) + (1,) * self.nd, (W, W, 1, C, C)),      # nn.Conv2d / nn.Conv3d(width, width, 1)
+                       (f"ws.{l}.bias", (W,), (1, W, 1, 1, C))]
+        params += [("fc1.weight", (HEAD_DIM, W), (HEAD_DIM, W, 1, HEAD_DIM, C)),
+                   ("fc1.bias", (HEAD_DIM,), (1, HEAD_DIM, 1, 1, HEAD_DIM)),
+                   ("fc2.weight", (O, HEAD_DIM), (O, HEAD_DIM, 1, O, HEAD_DIM)),
+                   ("fc2.bias", (O,), (1, O, 1, 1, O))]
+        self._register(params)
+        self._reset_state()
 
-    # the planes hold one [2][C][C] block per retained mode
-    def bind(self, params):
-        dev_before = self.device
-        super().bind(params)
-        if self.device != dev_before:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            n = 2 * self.Ktot * self.C * self.C
-            self.planes = [(torch.empty(n, **f32), torch.empty(n, **f32)) for _ in range(self.L)]
-
-    def _prepare_weights(self, st):
-        lib = _lib.get_lib()
-        self._refresh_pointers()
-        self._packed = True
-        if self._n_pad:
-            self._k("pad_copy", lib.ffno_pad_copy, _p(self._ptab), self._n_pad, 1, st)
+    def _pack_planes(self, lib, st):
         for l in range(self.L):
             w = [_p(self._pp(f"convs.{l}.weights{j}")) for j in range(1, self.nw + 1)]
             if self.nd == 2:
@@ -127,33 +92,21 @@ class GeoFNO2DEngine(ZongyiEngine):
         ws.P_in, ws.P = B * int(np.prod(S)), B * int(np.prod(Sp))
         s3, p3 = (1,) * (3 - nd) + tuple(S), (1,) * (3 - nd) + Sp
         ws.padmap = _capi.PadMap((ctypes.c_int32 * 3)(*s3), (ctypes.c_int32 * 3)(*p3))
-        # last-axis (real) transform: lines = everything but the last axis
-        lines = B * int(np.prod(Sp[:-1]))
-        ws.v = v = _View(lines // Sp[-2], Sp[-2], Sp[-1], 0, self.K, C)
-        ws.spec_z = self.K * lines * 2 * C                        # [kz][line][2][C]
-        ws.spec = self.Ktot * B * 2 * C                           # [mode][b][2][C]
+        ws.chain = ch = CornerChain(B, Sp, Ks, C, lambda *a: self._k(*a), self.device)
         P, P_in = ws.P, ws.P_in
-        ws.SYa, ws.SYb = torch.empty(ws.spec_z, **f32), torch.empty(ws.spec_z, **f32)
-        ws.SY, ws.SD = torch.empty(ws.spec, **f32), torch.empty(ws.spec, **f32)
-        if nd == 2:
-            ws.CW = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, self.Kx, self.Ky)), **f32)   # first-axis DFT scratch
-        else:
-            X1 = Sp[0]
-            ws.spec_y = self.Kz * 2 * self.Ky * B * X1 * 2 * C    # after the y transform: [kz][ky'][(b, x)][2][C]
-            ws.SYc, ws.SYd = torch.empty(ws.spec_y, **f32), torch.empty(ws.spec_y, **f32)
-            ws.CW = torch.empty(max(int(lib.ffno_cdft_rows_ws_floats(B * X1, C, self.Ky, self.Kz)),
-                                    int(lib.ffno_cdft_rows_ws_floats(B, C, self.Kx, self.Kz * 2 * self.Ky))), **f32)
+        ws.scr = ch.scratch(lambda n: torch.empty(n, **f32))
+        ws.SY, ws.SD = torch.empty(ch.spec, **f32), torch.empty(ch.spec, **f32)     # mixed / adjoint spectrum [mode][b][2][C]
         ws.Sb = torch.empty(P, C, **f32)
         ws.x = torch.empty(P_in, self.Cin, **f32)
         ws.X = torch.zeros(L + 1, P, C, **f32)           # X[0]: fc0 output in the padded frame (pad stays 0 for ever)
         ws.PRE = torch.empty(L, P, C, **f32)             # pre-activations (GELU derivative); last layer: unused
-        ws.SX = torch.empty(L, ws.spec, **f32)
+        ws.SX = torch.empty(L, ch.spec, **f32)
         ws.XC = torch.empty(P_in, C, **f32)              # cropped X[L]
         ws.H, ws.HPRE = torch.empty(P_in, HEAD_DIM, **f32), torch.empty(P_in, HEAD_DIM, **f32)
         ws.DH, ws.GC = torch.empty(P_in, HEAD_DIM, **f32), torch.empty(P_in, C, **f32)
         ws.G = [torch.zeros(P, C, **f32) for _ in range(2)]
         ws.DP = torch.empty(P, C, **f32)
-        ws.fwpart = torch.empty(2 * self.Ktot * C * C, **f32)
+        ws.fwpart = torch.empty(ch.planes_floats, **f32)
         ws.part = torch.empty(int(lib.ffno_plin_wgrad_partial_floats(P, C, HEAD_DIM)), **f32)
         ws.nsplit_lift = max(1, min(1024, (P_in + 127) // 128))
         ws.liftpart = torch.empty(ws.nsplit_lift * C * (self.Cin + 1), **f32)
@@ -161,37 +114,6 @@ class GeoFNO2DEngine(ZongyiEngine):
         while len(self._ws) > 3:
             self._ws.pop(next(iter(self._ws)))
         return ws
-
-    def _spectral(self, ws, src, dst, save, planes, fwd: bool, accumulate: int, st, resid=None):
-        """dst (+)= irfftn(corner-mix(rfftn(src))) on the padded grid (mesh_2d.py:38-53, mesh_3d.py:38-61), or its adjoint."""
-        lib = _lib.get_lib()
-        v, C, B = ws.v, self.C, ws.P // int(np.prod(ws.Sp))
-        tw = self._twiddle(v.L)
-        ck_f, ck_i, conj = (0, 1, 0) if fwd else (1, 0, 1)
-        self._k("dft_fwd", lib.ffno_dft_fwd, _p(src), _p(ws.SYa), _p(tw), v.Bv, v.Mv, v.Nv, C, self.K, 0, ck_f, st)
-        if self.nd == 2:
-            M = ws.Sp[0]
-            twm = self._twiddle(M)
-            self._k("cdft_rows", lib.ffno_cdft_rows_mfma, _p(ws.SYa), _p(save), _p(ws.CW), _p(twm), B, M, C, self.Kx, self.Ky, 0,
-                    st)
-            self._k("mode_mix", lib.ffno_mode_mix, _p(save), _p(planes), _p(ws.SY), B, C, self.Ktot, conj, st)
-            self._k("cdft_rows", lib.ffno_cdft_rows_mfma, _p(ws.SY), _p(ws.SYb), _p(ws.CW), _p(twm), B, M, C, self.Kx, self.Ky, 1,
-                    st)
-        else:
-            X1, Y1 = ws.Sp[0], ws.Sp[1]
-            twy, twx = self._twiddle(Y1), self._twiddle(X1)
-            KyK = self.Kz * 2 * self.Ky             # "columns" of the x transform: the (kz, ky') pairs
-            self._k("cdft_rows(y)", lib.ffno_cdft_rows_mfma, _p(ws.SYa), _p(ws.SYc), _p(ws.CW), _p(twy), B * X1, Y1, C, self.Ky,
-                    self.Kz, 0, st)
-            self._k("cdft_rows(x)", lib.ffno_cdft_rows_mfma, _p(ws.SYc), _p(save), _p(ws.CW), _p(twx), B, X1, C, self.Kx, KyK, 0,
-                    st)
-            self._k("mode_mix", lib.ffno_mode_mix, _p(save), _p(planes), _p(ws.SY), B, C, self.Ktot, conj, st)
-            self._k("cdft_rows(x)", lib.ffno_cdft_rows_mfma, _p(ws.SY), _p(ws.SYd), _p(ws.CW), _p(twx), B, X1, C, self.Kx, KyK, 1,
-                    st)
-            self._k("cdft_rows(y)", lib.ffno_cdft_rows_mfma, _p(ws.SYd), _p(ws.SYb), _p(ws.CW), _p(twy), B * X1, Y1, C, self.Ky,
-                    self.Kz, 1, st)
-        self._k("dft_inv", lib.ffno_dft_inv, _p(ws.SYb), _p(dst), _p(resid), _p(tw), v.Bv, v.Mv, v.Nv, C, self.K, 0, ck_i,
-                accumulate, st)
 
     @staticmethod
     def _inner(t, B, Sp, S, C):
@@ -220,7 +142,8 @@ class GeoFNO2DEngine(ZongyiEngine):
         self._k("fc0", lib.ffno_lift_fwd, _p(ws.x), _p(pp("fc0.weight")), _p(pp("fc0.bias")), _p(ws.X[0]), P_in, Cin, C, pm, None, st)
         for l in range(L):
             last = l == L - 1
-            self._spectral(ws, ws.X[l], ws.Sb, ws.SX[l], self.planes[l][0], True, 0, st)
+            # Sb = irfftn(corner-mix(rfftn(X[l]))) on the padded grid (mesh_2d.py:38-53, mesh_3d.py:38-61)
+            ws.chain.conv(ws.X[l], ws.Sb, ws.SX[l], ws.SY, self.planes[l][0], ws.scr, True, st)
             # x = conv(x) + w(x), GELU except after the last layer (mesh_2d.py:88-93, mesh_3d.py:93-98)
             self._k("layer_conv1x1", lib.ffno_plin_fwd, _p(ws.X[l]), C, _p(pp(f"ws.{l}.weight")), _p(pp(f"ws.{l}.bias")),
                     _p(ws.Sb), _p(ws.X[l + 1]), C, None, None, None if last else _p(ws.PRE[l]), P, C, C,
@@ -269,9 +192,8 @@ class GeoFNO2DEngine(ZongyiEngine):
                     _p(gp(f"ws.{l}.weight")), _p(gp(f"ws.{l}.bias")), P, C, C, 0, mode, st)
             self._k("layer_conv1x1_bwd", lib.ffno_plin_bwd_data, _p(g), C, _p(act), _p(pp(f"ws.{l}.weight")), _p(gn), C,
                     _p(ws.DP), P, C, C, 0, mode, st)
-            self._spectral(ws, ws.DP, gn, ws.SD, self.planes[l][1], False, 1, st)
-            self._k("fw_grad_partial", lib.ffno_fw_grad_partial, _p(ws.SX[l]), _p(ws.SD), _p(ws.fwpart), B, C, self.Ktot, 1, 0, 1,
-                    ws.spec, ws.spec, st)
+            ws.chain.conv(ws.DP, gn, ws.SD, ws.SY, self.planes[l][1], ws.scr, False, st, accumulate=1)
+            ws.chain.fw_grad_partial(ws.SX[l], ws.SD, ws.fwpart, st)
             gw = [_p(gp(f"convs.{l}.weights{j}")) for j in range(1, self.nw + 1)]
             if self.nd == 2:
                 self._k("fw2d_grad_reduce", lib.ffno_fw2d_grad_reduce2, _p(ws.fwpart), *gw, C, self.Kx, self.Ky, 1, 0, st)

@@ -3,7 +3,7 @@
 Reference: fourierflow/modules/zongyi_fno/grid_2d.py:16-78 (SpectralConv2d: rfft2 -> two K x K corner blocks ->
 irfft2, plus a pointwise linear, ReLU) and :81-129 (FNOZongyi2DBlock: in_proj, n_layers of those, a
 Linear-ReLU-Linear head).  The spectral convolution is the same operator as FNOPlus2DBlock's, so it runs on the same
-kernels (ffno_dft_fwd -> ffno_cdft_rows -> ffno_mode_mix -> ffno_cdft_rows(inverse) -> ffno_dft_inv); everything
+kernels, the corner chain of _corner_chain.py; everything
 pointwise runs on csrc/plin.hip.  The baseline is 20 channels wide: activations and weights live in buffers padded
 to the 32- (or 64-) channel tiles of the spectral kernels with exact zeros in the pad, one ffno_pad_copy launch
 moves all parameters into their padded twins before a pass and all gradients back after it.
@@ -14,14 +14,14 @@ Unlike the F-FNO engine this one returns the INPUT gradient as well and keeps se
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict
 
 import numpy as np
 import torch
 
 from . import _capi, _lib
-from .engine import _p, _View
+from ._corner_chain import CornerChain
+from .engine import _p
 
 HEAD_DIM = 128
 
@@ -37,29 +37,28 @@ class ZongyiEngine:
         self.residual, self.conv_residual = bool(residual), bool(conv_residual)
         self.C = 32            # channel tile of the spectral kernels; channels width..31 are exact zeros
         self.O = 1
-        W, K = width, modes
-        self.param_names, self.param_shapes = [], {}
-        # (R, Cc, inner) of the plain tensor and (Rp, Cp) of its padded twin, per parameter
-        self._pad_geom = {}
-
-        def add(name, shape, geom):
-            self.param_names.append(name)
-            self.param_shapes[name] = tuple(shape)
-            self._pad_geom[name] = geom
-
-        C = self.C
-        add("in_proj.weight", (W, input_dim), (W, input_dim, 1, C, input_dim))
-        add("in_proj.bias", (W,), (1, W, 1, 1, C))
+        self.Ktot = 2 * modes * modes      # retained (ky, kx') modes: one [2][C][C] block of the planes each
+        W, K, C = width, modes, self.C
+        params = [("in_proj.weight", (W, input_dim), (W, input_dim, 1, C, input_dim)),
+                  ("in_proj.bias", (W,), (1, W, 1, 1, C))]
         for l in range(n_layers):
             pre = f"spectral_layers.{l}."
-            add(pre + "linear.weight", (W, W), (W, W, 1, C, C))
-            add(pre + "linear.bias", (W,), (1, W, 1, 1, C))
-            for j in range(2):
-                add(pre + f"fourier_weight.{j}", (W, W, K, K, 2), (W, W, K * K * 2, C, C))
-        add("feedforward.0.weight", (HEAD_DIM, W), (HEAD_DIM, W, 1, HEAD_DIM, C))
-        add("feedforward.0.bias", (HEAD_DIM,), (1, HEAD_DIM, 1, 1, HEAD_DIM))
-        add("feedforward.2.weight", (1, HEAD_DIM), (1, HEAD_DIM, 1, 1, HEAD_DIM))
-        add("feedforward.2.bias", (1,), (1, 1, 1, 1, 1))
+            params += [(pre + "linear.weight", (W, W), (W, W, 1, C, C)),
+                       (pre + "linear.bias", (W,), (1, W, 1, 1, C))]
+            params += [(pre + f"fourier_weight.{j}", (W, W, K, K, 2), (W, W, K * K * 2, C, C)) for j in range(2)]
+        params += [("feedforward.0.weight", (HEAD_DIM, W), (HEAD_DIM, W, 1, HEAD_DIM, C)),
+                   ("feedforward.0.bias", (HEAD_DIM,), (1, HEAD_DIM, 1, 1, HEAD_DIM)),
+                   ("feedforward.2.weight", (1, HEAD_DIM), (1, HEAD_DIM, 1, 1, HEAD_DIM)),
+                   ("feedforward.2.bias", (1,), (1, 1, 1, 1, 1))]
+        self._register(params)
+        self._reset_state()
+
+    def _register(self, params):
+        """``params``: (name, shape, pad geometry) in registration order; the pad geometry is (R, Cc, inner) of the plain tensor
+        and (Rp, Cp) of its padded twin.  Lays out the flat gradient buffer and the padded twins."""
+        self.param_names = [n for n, _, _ in params]
+        self.param_shapes = {n: tuple(shape) for n, shape, _ in params}
+        self._pad_geom = {n: geom for n, _, geom in params}
         self._offsets, off = {}, 0
         self._poffsets, poff = {}, 0
         for n in self.param_names:
@@ -69,13 +68,15 @@ class ZongyiEngine:
             self._poffsets[n] = poff
             poff += Rp * Cp * inner
         self.n_params, self.n_padded = off, poff
+
+    def _reset_state(self):
+        """The state of an engine nothing is bound to yet."""
         self.params: Dict[str, torch.Tensor] = {}
         self.device = None
         self.timer = None
         self._issue_stream = 0
         self.paired_last = False
         self._ws = {}
-        self._tw = {}
         self._ptr_sig = None
         self._packed = False
 
@@ -116,10 +117,9 @@ class ZongyiEngine:
             self.gflat = torch.zeros(self.n_params, **f32)
             self.ppad = torch.zeros(self.n_padded, **f32)      # padded parameters (pad entries stay 0 forever)
             self.gpad = torch.zeros(self.n_padded, **f32)      # padded gradients
-            K2 = 2 * self.K * self.K
-            self.planes = [(torch.empty(2 * K2 * self.C * self.C, **f32), torch.empty(2 * K2 * self.C * self.C, **f32))
-                           for _ in range(self.L)]
-            self._ws, self._tw = {}, {}
+            n = 2 * self.Ktot * self.C * self.C
+            self.planes = [(torch.empty(n, **f32), torch.empty(n, **f32)) for _ in range(self.L)]
+            self._ws = {}
         self._ptr_sig = None
 
     def zero_grad(self):
@@ -165,13 +165,6 @@ class ZongyiEngine:
         self._ptab = table(lambda n: self.params[n], self.ppad)
         self._gtab = table(self.grad_view, self.gpad)
 
-    def _twiddle(self, L: int) -> torch.Tensor:
-        if L not in self._tw:
-            host = np.zeros(2 * L, np.float32)
-            _capi.check(_lib.get_lib().ffno_twiddle_fill_host(host.ctypes.data_as(ctypes.c_void_p), L), "twiddle")
-            self._tw[L] = torch.from_numpy(host).to(self.device)
-        return self._tw[L]
-
     # ------------------------------------------------------------------------------------------------
     def _workspace(self, B, M, N, n_slots):
         key = (B, M, N)
@@ -190,17 +183,11 @@ class ZongyiEngine:
             ws = type("WS", (), {})()
             P = B * M * N
             ws.P = P
-            v = _View(B, M, N, 0, self.K, C)
-            v.R, v.K2 = B, 2 * self.K * self.K
-            v.spec_y = v.spec
-            v.spec = v.K2 * B * 2 * C
-            ws.v = v
-            ws.SYa = torch.empty(v.spec_y, **f32)
-            ws.SYb = torch.empty(v.spec_y, **f32)
-            ws.CW = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, self.K, self.K)), **f32)     # first-axis DFT scratch
-            ws.SY = torch.empty(v.spec, **f32)
-            ws.SX0 = torch.empty(v.spec, **f32)             # forward spectrum when nothing is saved
-            ws.SD = torch.empty(v.spec, **f32)              # adjoint spectrum dY of the current layer
+            ws.chain = ch = CornerChain(B, (M, N), (self.K, self.K), C, lambda *a: self._k(*a), self.device)
+            ws.scr = ch.scratch(lambda n: torch.empty(n, **f32))
+            ws.SY = torch.empty(ch.spec, **f32)             # mixed spectrum
+            ws.SX0 = torch.empty(ch.spec, **f32)            # forward spectrum when nothing is saved
+            ws.SD = torch.empty(ch.spec, **f32)             # adjoint spectrum dY of the current layer
             ws.S = torch.empty(P, C, **f32)                 # spectral branch output of the current layer
             ws.Xa = [torch.empty(P, C, **f32) for _ in range(2)]     # inference ping-pong
             ws.A0 = torch.empty(P, C, **f32) if self.residual else None   # layer output before the block-level residual
@@ -208,7 +195,7 @@ class ZongyiEngine:
             ws.G = [torch.empty(P, C, **f32) for _ in range(2)]
             ws.DP = torch.empty(P, C, **f32)
             ws.DH = torch.empty(P, HEAD_DIM, **f32)
-            ws.fwpart = torch.empty(2 * v.K2 * C * C, **f32)
+            ws.fwpart = torch.empty(ch.planes_floats, **f32)
             ws.part = torch.empty(int(lib.ffno_plin_wgrad_partial_floats(P, C, HEAD_DIM)), **f32)
             ws.slots = []
             self._ws[key] = ws
@@ -218,7 +205,7 @@ class ZongyiEngine:
             s = type("Slot", (), {})()
             s.x = torch.empty(ws.P, self.Cin, **f32)
             s.X = torch.empty(L + 1, ws.P, C, **f32)        # X[0] = in_proj(x), X[l+1] = output of layer l
-            s.SX = torch.empty(L, ws.v.spec, **f32)          # forward 2-D spectra (inputs of the weight gradient)
+            s.SX = torch.empty(L, ws.chain.spec, **f32)      # forward 2-D spectra (inputs of the weight gradient)
             s.H = torch.empty(ws.P, HEAD_DIM, **f32)
             s.A = torch.empty(L, ws.P, C, **f32) if self.residual else None          # relu outputs (ReLU masks)
             s.S = torch.empty(L, ws.P, C, **f32) if not self.conv_residual else None # spectral outputs (inputs of `linear`)
@@ -226,26 +213,15 @@ class ZongyiEngine:
             ws.slots.append(s)
         return ws
 
-    def _spectral(self, ws, src, dst, save, planes, fwd: bool, accumulate: int, st, resid=None):
-        """dst (+)= irfft2(corner-mix(rfft2(src)))  (or its adjoint), grid_2d.py:48-71."""
-        lib = _lib.get_lib()
-        v, C = ws.v, self.C
-        tw = self._twiddle(v.L)
-        ck_f, ck_i, conj = (0, 1, 0) if fwd else (1, 0, 1)
-        self._k("dft_fwd", lib.ffno_dft_fwd, _p(src), _p(ws.SYa), _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, 0, ck_f, st)
-        twm = self._twiddle(v.Mv)
-        self._k("cdft_rows", lib.ffno_cdft_rows_mfma, _p(ws.SYa), _p(save), _p(ws.CW), _p(twm), v.Bv, v.Mv, C, v.K, v.K, 0, st)
-        self._k("mode_mix", lib.ffno_mode_mix, _p(save), _p(planes), _p(ws.SY), v.Bv, C, v.K2, conj, st)
-        self._k("cdft_rows", lib.ffno_cdft_rows_mfma, _p(ws.SY), _p(ws.SYb), _p(ws.CW), _p(twm), v.Bv, v.Mv, C, v.K, v.K, 1, st)
-        self._k("dft_inv", lib.ffno_dft_inv, _p(ws.SYb), _p(dst), _p(resid), _p(tw), v.Bv, v.Mv, v.Nv, C, v.K, 0, ck_i,
-                accumulate, st)
-
     def _prepare_weights(self, st):
         lib = _lib.get_lib()
         self._refresh_pointers()
         self._packed = True
         if self._n_pad:
             self._k("pad_copy", lib.ffno_pad_copy, _p(self._ptab), self._n_pad, 1, st)
+        self._pack_planes(lib, st)
+
+    def _pack_planes(self, lib, st):
         for l in range(self.L):
             pre = f"spectral_layers.{l}."
             self._k("fw2d_pack", lib.ffno_fw2d_pack, _p(self._pp(pre + "fourier_weight.0")),
@@ -284,7 +260,8 @@ class ZongyiEngine:
             pre = f"spectral_layers.{l}."
             nxt = X[l + 1] if X is not None else ws.Xa[(l + 1) & 1]
             S = sl.S[l] if (save_for_backward and not self.conv_residual) else ws.S
-            self._spectral(ws, cur, S, sl.SX[l] if save_for_backward else ws.SX0, self.planes[l][0], True, 0, st)
+            # S = irfft2(corner-mix(rfft2(cur)))   (grid_2d.py:48-71)
+            ws.chain.conv(cur, S, sl.SX[l] if save_for_backward else ws.SX0, ws.SY, self.planes[l][0], ws.scr, True, st)
             # conv_residual: act(spectral(x) + linear(x)), else act(linear(spectral(x)))   (grid_2d.py:74-77);
             # block-level residual: x = layer(x) + x as a second output, the ReLU output itself is kept for the mask (:126)
             A = nxt if not self.residual else (sl.A[l] if save_for_backward else ws.A0)
@@ -330,7 +307,6 @@ class ZongyiEngine:
         self._k("head_fc1_bwd", lib.ffno_plin_bwd_data, _p(ws.DH), HEAD_DIM, _p(sl.H), _p(pp("feedforward.0.weight")), _p(g), C,
                 None, P, C, HEAD_DIM, 0, 1, st)
         cur = 0
-        v = ws.v
         for l in range(L - 1, -1, -1):
             pre = f"spectral_layers.{l}."
             xin = sl.X[l]
@@ -344,13 +320,12 @@ class ZongyiEngine:
                 # dpre = g * 1[out > 0] feeds both the linear (here) and the spectral adjoint (below)
                 self._k("layer_linear_bwd", lib.ffno_plin_bwd_data, _p(g), C, _p(act), _p(pp(pre + "linear.weight")), _p(gn),
                         C, _p(ws.DP), P, C, C, 0, 1, st)
-                self._spectral(ws, ws.DP, gn, ws.SD, self.planes[l][1], False, 1, st, resid=res)
+                ws.chain.conv(ws.DP, gn, ws.SD, ws.SY, self.planes[l][1], ws.scr, False, st, resid=res, accumulate=1)
             else:
                 self._k("layer_linear_bwd", lib.ffno_plin_bwd_data, _p(g), C, _p(act), _p(pp(pre + "linear.weight")),
                         _p(ws.DP), C, None, P, C, C, 0, 1, st)
-                self._spectral(ws, ws.DP, gn, ws.SD, self.planes[l][1], False, 0, st, resid=res)
-            self._k("fw_grad_partial", lib.ffno_fw_grad_partial, _p(sl.SX[l]), _p(ws.SD), _p(ws.fwpart), v.R, C, v.K2, 1, 0, 1,
-                    v.spec, v.spec, st)
+                ws.chain.conv(ws.DP, gn, ws.SD, ws.SY, self.planes[l][1], ws.scr, False, st, resid=res)
+            ws.chain.fw_grad_partial(sl.SX[l], ws.SD, ws.fwpart, st)
             self._k("fw2d_grad_reduce", lib.ffno_fw2d_grad_reduce, _p(ws.fwpart), _p(gp(pre + "fourier_weight.0")),
                     _p(gp(pre + "fourier_weight.1")), C, self.K, 1, acc, st)
             g, cur = gn, 1 - cur

@@ -7,23 +7,14 @@ methods (``SpectralConv2d.forward_fourier``, ``FeedForward.forward``); the whole
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
 
 from . import _capi, _lib
+from ._corner_chain import CornerChain, checked
 from .engine import MODES, _p
-
-_TW = {}
-
-
-def _twiddle(L: int, device) -> torch.Tensor:
-    key = (L, str(device), _lib.is_test_backend())
-    if key not in _TW:
-        host = np.zeros(2 * L, np.float32)
-        _capi.check(_lib.get_lib().ffno_twiddle_fill_host(host.ctypes.data_as(ctypes.c_void_p), L), "twiddle")
-        _TW[key] = torch.from_numpy(host).to(device)
-    return _TW[key]
 
 
 _SP2D_WS = {}
@@ -73,7 +64,7 @@ class _SpectralConv2dFn(torch.autograd.Function):
         st = _lib.current_stream(x.device)
         ws = _spectral2d_workspace(x, w_y, w_x, modes)
         out = torch.empty_like(x)
-        twn, twm = _twiddle(N, x.device), _twiddle(M, x.device)
+        twn, twm = _lib.twiddle(N, x.device), _lib.twiddle(M, x.device)
         _capi.check(lib.ffno_spectral2d_fwd(_p(x), _p(w_y), _p(w_x), _p(out), _p(ws), _p(twn), _p(twm), B, M, N, C,
                                             modes, mode_id, st), "spectral2d_fwd")
         ctx.save_for_backward(x, w_y, w_x)
@@ -93,7 +84,7 @@ class _SpectralConv2dFn(torch.autograd.Function):
         full = mode_id == MODES["full"]
         gwy = torch.empty_like(w_y) if full else None
         gwx = torch.empty_like(w_x) if full else None
-        twn, twm = _twiddle(N, x.device), _twiddle(M, x.device)
+        twn, twm = _lib.twiddle(N, x.device), _lib.twiddle(M, x.device)
         _capi.check(lib.ffno_spectral2d_bwd(_p(x), _p(w_y), _p(w_x), _p(gy), _p(gx), _p(gwy), _p(gwx), _p(ws), _p(twn),
                                             _p(twm), B, M, N, C, modes, mode_id, 0, 0, st), "spectral2d_bwd")
         return gx, gwy, gwx, None, None
@@ -421,39 +412,40 @@ def _points_major(z):
     return z.permute(2, 4, 1, 0, 3)
 
 
+@functools.lru_cache(maxsize=32)
+def _chain(B, Sp, Ks, C, device, emu) -> CornerChain:
+    """The chain of a shape and backend (geometry and table pointers only, so it is kept across calls)."""
+    return CornerChain(B, Sp, Ks, C, checked, device)
+
+
+def _scratch(ch):
+    """Per-call scratch of one half of the chain: the spectra between its stages and the row-transform scratch."""
+    f32 = dict(dtype=torch.float32, device=ch.device)
+    return [torch.empty(n, **f32) for n in ch.mid_sizes], torch.empty(ch.cw_floats, **f32)
+
+
 class _ModesToGridFn(torch.autograd.Function):
     """Z [m2, 2 m1, B, 2, C] (mode-major corners) -> channels-last grid [B, s1, s2, C] = irfft2 of the zero-padded spectrum."""
 
     @staticmethod
     def forward(ctx, z, s1, s2):
-        lib = _lib.get_lib()
         m2, R, B, _, C = z.shape
-        m1 = R // 2
-        st = _lib.current_stream(z.device)
-        f32 = dict(dtype=torch.float32, device=z.device)
+        ctx.chain = ch = _chain(B, (s1, s2), (R // 2, m2), C, z.device, _lib.is_test_backend())
         zs = (z * (1.0 / float(np.sqrt(s1 * s2)))).contiguous()
-        cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
-        sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
-        out = torch.empty(B, s1, s2, C, **f32)
-        _capi.check(lib.ffno_cdft_rows_mfma(_p(zs), _p(sy), _p(cw), _p(_twiddle(s1, z.device)), B, s1, C, m1, m2, 1, st), "cdft_rows")
-        _capi.check(lib.ffno_dft_inv(_p(sy), _p(out), None, _p(_twiddle(s2, z.device)), B, s1, s2, C, m2, 0, 1, 0, st), "dft_inv")
-        ctx.cfg = (s1, s2, m1, m2, B, C)
+        out = torch.empty(B, s1, s2, C, dtype=torch.float32, device=z.device)
+        mid, cw = _scratch(ch)
+        ch.synthesis(zs, mid, out, cw, True, _lib.current_stream(z.device))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.get_lib()
-        s1, s2, m1, m2, B, C = ctx.cfg
+        ch = ctx.chain
         g = g.contiguous()
-        st = _lib.current_stream(g.device)
-        f32 = dict(dtype=torch.float32, device=g.device)
-        cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
-        sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
-        dz = torch.empty(m2, 2 * m1, B, 2, C, **f32)
+        dz = torch.empty(ch.Ks[1], 2 * ch.Ks[0], ch.B, 2, ch.C, dtype=torch.float32, device=g.device)
+        mid, cw = _scratch(ch)
         # the adjoint of the zero-padded irfft (bins k >= 1 counted twice), then the adjoint of the inverse row transform
-        _capi.check(lib.ffno_dft_fwd(_p(g), _p(sy), _p(_twiddle(s2, g.device)), B, s1, s2, C, m2, 0, 1, st), "dft_fwd")
-        _capi.check(lib.ffno_cdft_rows_mfma(_p(sy), _p(dz), _p(cw), _p(_twiddle(s1, g.device)), B, s1, C, m1, m2, 0, st), "cdft_rows")
-        return dz * (1.0 / float(np.sqrt(s1 * s2))), None, None
+        ch.analysis(g, mid, dz, cw, False, _lib.current_stream(g.device))
+        return dz * (1.0 / float(np.sqrt(ch.Sp[0] * ch.Sp[1]))), None, None
 
 
 class _GridToMixedModesFn(torch.autograd.Function):
@@ -465,44 +457,37 @@ class _GridToMixedModesFn(torch.autograd.Function):
         lib = _lib.get_lib()
         B, s1, s2, C = x.shape
         m1, m2 = w1.shape[2], w1.shape[3]
-        K = 2 * m1 * m2
+        ctx.chain = ch = _chain(B, (s1, s2), (m1, m2), C, x.device, _lib.is_test_backend())
         st = _lib.current_stream(x.device)
         f32 = dict(dtype=torch.float32, device=x.device)
-        wp, wpt = torch.empty(2 * K * C * C, **f32), torch.empty(2 * K * C * C, **f32)
+        wp, wpt = torch.empty(ch.planes_floats, **f32), torch.empty(ch.planes_floats, **f32)
         _capi.check(lib.ffno_fw2d_pack2(_p(w1), _p(w2), _p(wp), _p(wpt), C, m1, m2, st), "fw2d_pack2")
-        cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
-        sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
-        sx, out = torch.empty(K * B * 2 * C, **f32), torch.empty(m2, 2 * m1, B, 2, C, **f32)
-        _capi.check(lib.ffno_dft_fwd(_p(x), _p(sy), _p(_twiddle(s2, x.device)), B, s1, s2, C, m2, 0, 0, st), "dft_fwd")
-        _capi.check(lib.ffno_cdft_rows_mfma(_p(sy), _p(sx), _p(cw), _p(_twiddle(s1, x.device)), B, s1, C, m1, m2, 0, st), "cdft_rows")
-        _capi.check(lib.ffno_mode_mix(_p(sx), _p(wp), _p(out), B, C, K, 0, st), "mode_mix")
+        mid, cw = _scratch(ch)
+        sx, out = torch.empty(ch.spec, **f32), torch.empty(m2, 2 * m1, B, 2, C, **f32)
+        ch.analysis(x, mid, sx, cw, True, st)
+        ch.mix(sx, wp, out, True, st)
         ctx.save_for_backward(sx, wpt)
-        ctx.cfg = (B, s1, s2, C, m1, m2)
         return out * float(np.sqrt(s1 * s2))
 
     @staticmethod
     def backward(ctx, g):
         lib = _lib.get_lib()
         sx, wpt = ctx.saved_tensors
-        B, s1, s2, C, m1, m2 = ctx.cfg
-        K = 2 * m1 * m2
+        ch = ctx.chain
+        (s1, s2), (m1, m2), B, C = ch.Sp, ch.Ks, ch.B, ch.C
         st = _lib.current_stream(g.device)
         f32 = dict(dtype=torch.float32, device=g.device)
         dy = (g * float(np.sqrt(s1 * s2))).contiguous()
         dx = None
         if ctx.needs_input_grad[0]:
-            dsx = torch.empty(K * B * 2 * C, **f32)
-            cw = torch.empty(int(lib.ffno_cdft_rows_ws_floats(B, C, m1, m2)), **f32)
-            sy = torch.empty(m2 * B * s1 * 2 * C, **f32)
+            dsx = torch.empty(ch.spec, **f32)
+            mid, cw = _scratch(ch)
             dx = torch.empty(B, s1, s2, C, **f32)
-            _capi.check(lib.ffno_mode_mix(_p(dy), _p(wpt), _p(dsx), B, C, K, 1, st), "mode_mix")
-            _capi.check(lib.ffno_cdft_rows_mfma(_p(dsx), _p(sy), _p(cw), _p(_twiddle(s1, g.device)), B, s1, C, m1, m2, 1, st),
-                        "cdft_rows")
-            _capi.check(lib.ffno_dft_inv(_p(sy), _p(dx), None, _p(_twiddle(s2, g.device)), B, s1, s2, C, m2, 0, 0, 0, st), "dft_inv")
-        part = torch.empty(2 * K * C * C, **f32)
+            ch.mix(dy, wpt, dsx, False, st)
+            ch.synthesis(dsx, mid, dx, cw, False, st)
+        part = torch.empty(ch.planes_floats, **f32)
         gw1, gw2 = torch.empty(C, C, m1, m2, 2, **f32), torch.empty(C, C, m1, m2, 2, **f32)
-        n = K * B * 2 * C
-        _capi.check(lib.ffno_fw_grad_partial(_p(sx), _p(dy), _p(part), B, C, K, 1, 0, 1, n, n, st), "fw_grad_partial")
+        ch.fw_grad_partial(sx, dy, part, st)
         _capi.check(lib.ffno_fw2d_grad_reduce2(_p(part), _p(gw1), _p(gw2), C, m1, m2, 1, 0, st), "fw2d_grad_reduce2")
         return dx, gw1, gw2
 

@@ -51,7 +51,7 @@ def main():
         t_op = timeit(lambda: ops.spectral_conv2d(x, w0, w1, K))
     # the C entry point itself (no autograd.Function, no workspace lookup): what a non-Python host pays
     wsd = ops._spectral2d_workspace(x, w0, w1, K)
-    twn_, twm_ = ops._twiddle(N, x.device), ops._twiddle(M, x.device)
+    twn_, twm_ = _lib.twiddle(N, x.device), _lib.twiddle(M, x.device)
     yd = torch.empty_like(x)
     P_ = ctypes.c_void_p
     t_c = timeit(lambda: lib.ffno_spectral2d_fwd(P_(x.data_ptr()), P_(w0.data_ptr()), P_(w1.data_ptr()), P_(yd.data_ptr()), P_(wsd.data_ptr()),
