@@ -118,6 +118,31 @@ def twiddle(L: int, device):
     return _twiddles[key]
 
 
+def device_table(struct, rows, device):
+    """A descriptor table (a list of ctypes ``struct`` values) as device bytes."""
+    import numpy as np
+    import torch
+    arr = (struct * len(rows))(*rows)
+    return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
+
+
+class CachedTable:
+    """A descriptor table and the rows it was built from: rebuilt only when the rows changed (parameters re-bound, a new workspace)."""
+    __slots__ = ("rows", "table")
+
+    def __init__(self):
+        self.rows = self.table = None
+
+    def get(self, struct, rows: tuple, device=None):
+        """``rows``: one tuple of ``struct``'s fields per entry.  ``device`` None: a HOST array (for the entry points that copy
+        their table into the kernel arguments at enqueue)."""
+        if rows != self.rows:
+            items = [struct(*r) for r in rows]
+            self.table = (struct * len(items))(*items) if device is None else device_table(struct, items, device)
+            self.rows = rows
+        return self.table
+
+
 def require_device_tensor(t, what: str):
     import torch
     if _test_backend is not None:

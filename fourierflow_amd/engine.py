@@ -32,7 +32,7 @@ from ._corner_chain import CornerChain
 
 MODES = {"full": 0, "low-pass": 1, "no-fourier": 2}
 HEAD_DIM = 128  # grid_2d.py:150-152 / mesh_3d.py:155-157: WNLinear(width, 128) -> WNLinear(128, out)
-_SUPPORTED_CH = {(64, 256), (64, 128), (32, 128), (32, 64)}
+_SUPPORTED_CH = {(64, 256), (64, 128), (32, 128), (32, 64)}      # = what ffno_ffx_supported takes (csrc/ffx.hip FFNO_FX_DISPATCH)
 # paired spectral launch, workgroup -> (branch, tile) map (ffno_spectral_x3_pair `interleave`): bit 1 = image-local where the shapes
 # allow it (the workgroups that read one image share an XCD, so the image crosses HBM once: PMC traffic 178.9 -> 150.7 MB per launch,
 # round 2), else bit 0 = even workgroups branch a, odd ones branch b
@@ -92,13 +92,13 @@ _Saved = collections.namedtuple("_Saved", "x B S ws ws_key plan")
 
 
 class _Linear:
-    __slots__ = ("prefix", "rows", "cols", "wnorm", "weff", "gweff", "wt", "fx")
+    __slots__ = ("prefix", "rows", "cols", "wnorm", "weff", "gweff", "fx")
 
     def __init__(self, prefix, rows, cols, wnorm):
         self.prefix, self.rows, self.cols, self.wnorm = prefix, rows, cols, wnorm
         self.weff = None   # effective weight [rows, cols] (after weight-norm)
         self.gweff = None  # gradient w.r.t. the effective weight
-        self.wt = None     # transposed effective weight [cols, rows] (feed-forward linears only; backward)
+        self.fx = None     # the four operand packs of the feed-forward block this linear belongs to (forward A1/A2, backward A1/A2)
 
 
 class _View:
@@ -111,6 +111,94 @@ class _View:
         self.R = Bv * Mv if a01 == 0 else Bv * Nv
         self.spec = K * self.R * 2 * C
         self.modes = K      # what the mix and the weight gradient run over
+        self.x3fmt = None   # format of the packed x3 weight set this axis reads (ffno.h FFNO_PLANES_*): set by every pass's plan
+
+
+class _DeferredWord:
+    """One device word that is looked at a round late: copied to pinned host memory behind the work in flight, with an event
+    recorded after the copy, and read the next time round once the event has passed -- no synchronisation."""
+
+    def __init__(self, device):
+        self.host = torch.zeros(1, dtype=torch.int32)
+        if device is not None and device.type == "cuda":
+            self.host = self.host.pin_memory()
+        self.event = None
+        self.pending = False
+
+    def post(self, word: torch.Tensor):
+        """Start the copy of ``word`` (one int32 on the device) on the current stream."""
+        self.host.copy_(word, non_blocking=True)
+        self.event = torch.cuda.Event() if word.is_cuda else None      # (the emulator backend: the copy is done by now)
+        if self.event is not None:
+            self.event.record()
+        self.pending = True
+
+    def take(self) -> Optional[torch.Tensor]:
+        """The host copy, once, when a posted copy has landed; None while there is nothing new to look at."""
+        if not self.pending or (self.event is not None and not self.event.query()):
+            return None
+        self.pending = False
+        return self.host
+
+
+class _Workspace:
+    """The device buffers and per-geometry schedule decisions of one (batch, grid, save) key, every field named once.  A field the
+    configuration does not need stays None.  (A plain class, not __slots__: bench.py and tools/power_trace.py walk a workspace's
+    tensors through vars().)"""
+
+    def __init__(self):
+        self.P = self.P_in = None        # pixels of the (padded) activation buffers / of the inputs and outputs
+        self.Sp = None                   # padded grid
+        self.views = None                # one _View per spatial axis (spectral="plus": the one CornerChain)
+        self.padmap = self.pm = None     # _capi.PadMap of a padded operator, and byref() of it: the argument the kernels take
+        self.X = None                    # running activation
+        self.Blast = None                # the last layer's output (head input)
+        self.Y = None                    # head output
+        self.S = None                    # feed-forward inputs (spectral-branch outputs), per saved layer
+        self.SXall = self.SDall = None   # forward / adjoint spectra, per axis, layer-major (kept for the Fourier-weight gradient)
+        self.SY = self.SD = None         # scratch spectra of the staged path (mixed / stage-A)
+        self.SY2 = self.SD2 = None       # ... of the second branch of a paired STAGE launch
+        self.T = self.G1 = None          # output of the second branch of a paired launch / of the second adjoint branch
+        self.TS = None                   # lazy sums: the second branch output of every layer
+        self.chain = self.scr = None     # spectral="plus": the corner chain (= views[0]) and its scratch
+        self.mask_words = None           # int32 words of one layer's packed ReLU sign bits
+        # range words, one per (tensor kind, layer): x = layer inputs, s = spectral-branch outputs (feed-forward inputs),
+        # g = running gradient (both buffers), d = feed-forward data gradients, t / f = LayerNorm / fork-head gradients
+        self.rw_kinds = self.RW = None
+        self.rw_bwd_clean = False        # the backward's words are still zero from the forward's clearing launch
+        self.TL = self.LNS = None        # LayerNorm: feed-forward outputs before it; {mean, rstd} per pixel
+        self.TLF = self.LNSF = None      # ... of the forecast feed-forwards (they end in their own LayerNorm, feedforward.py:18-19)
+        self.DT = self.DTF = None        # LayerNorm backward: gradients before it (backcast / forecast)
+        self.lnpart = None               # ... its partial slices
+        self.F = self.YL = None          # fork heads: forecast_ff outputs f_l (inputs of the shared head); per-layer head outputs
+        self.MASKF = self.DSF = None     # fork heads, backward: sign bits, data gradient
+        self.GF = self.redl = None       # ... head gradient, per-layer head reduction
+        self.HG = None                   # general feed-forward: kept hidden activations per block kind / saved layer / hidden layer
+        self.DA = self.glpart = None     # ... backward: ping-pong hidden gradients, weight-gradient slices
+        self.MASK = None                 # packed ReLU sign bits per saved layer
+        self.DS = None                   # feed-forward data gradient
+        # running gradient: a ping-pong pair -- or one buffer per layer when the weight-gradient launches are deferred to the end
+        # of the pass (they read every layer's summed gradient then)
+        self.G = self.defer_wgrad = None
+        self.lazy_sums = None            # "s": the chain kernels leave their input sums to the deferred weight-gradient launch
+        self.nsplit_ff = self.nsplit_ffm = None      # feed-forward weight gradient: slices per layer launch / of the all-layers launch
+        self.ffpart = None               # ... its partial sums
+        # split-bf16 path with per-layer feed-forwards: every layer keeps its own slices and ONE batched launch reduces them all
+        # at the end of the backward pass (24 kernel boundaries less per step)
+        self.defer_reduce = self.ffparts = None
+        self.wg_jobs = self.wg_table = None      # rows of the deferred weight-gradient launch in this backward pass (None: per layer); its table
+        self.red_jobs = self.red_table = None    # rows of the batched reduce launch in this backward pass; its table
+        self.nsplit_fw = self.fwpart = None      # Fourier-weight gradient: slices per axis, partial sums per (weight set, axis)
+        # ... per-layer weights, per axis: partial sums, device table of the layers' gradient pointers, the pointers it was built from
+        self.fwpart_multi = self.fwgrad_tab = self.fwgrad_sig = None
+        self.nsplit_lift = self.liftpart = None      # lift weight gradient: slices, partial sums
+        self.nsplit_head = self.headpart = None      # head weight gradient: slices, partial sums
+        self.red = None                  # ... its reduction
+        self.MIX = None                  # inference layer: the mixed spectra of the two axes
+        self.stack_sync = None           # persistent inference stack: barrier words (the last one is the error word)
+        self.stack_late = None           # ... its late look at that word (_DeferredWord)
+        self.stack_checked = False       # ... the first launch was checked
+        self.stack_calls = 0             # ... launches so far
 
 
 class FFNOEngine:
@@ -152,7 +240,6 @@ class FFNOEngine:
         self.n_ff, self.dropout, self.in_dropout = int(n_ff_layers), float(dropout), float(in_dropout)
         self.general_ff = self.n_ff != 2 or self.dropout > 0.0
         self.drop_seed = int(torch.initial_seed()) & 0x7FFFFFFF      # base seed of the dropout masks (tests may set it)
-        self._drop_calls = 0                                          # training forwards so far: every one draws new masks
         # FeedForward(layer_norm=True): nn.LayerNorm(width) after the last linear of every feed-forward (feedforward.py:18-19)
         self.layer_norm = bool(layer_norm)
         if spectral not in ("factorized", "plus", "dct"):
@@ -175,6 +262,9 @@ class FFNOEngine:
         self.mode, self.mode_id = mode, MODES[mode]
         self.share_weight, self.share_fork, self.wnorm = share_weight, share_fork, ff_weight_norm
         self.use_fork = use_fork   # per-layer forecast heads: forecast = sum_l out(forecast_ff_l(s_l))  (grid_2d.py:164-167)
+        # every layer is spectral branches + ONE two-linear feed-forward with the residual: what the paired / per-layer-call /
+        # deferred / inference schedules are written for
+        self._plain_layer = not (use_fork or self.layer_norm or self.general_ff)
 
         # ---- parameter inventory, in the reference's named_parameters() naming --------------------
         self.linears: Dict[str, _Linear] = {}
@@ -237,20 +327,12 @@ class FFNOEngine:
         # weight set of every layer (0 without Fourier weights: no planes are read then)
         self._fw_set_of = [self._fw_sets.index(names) for names in self.fw_names] or [0] * n_layers
 
-        self.params: Dict[str, torch.Tensor] = {}
-        self.device = None
-        self._ptr_sig = None
-        self._ws_key = None
-        self._tw: Dict[int, torch.Tensor] = {}
-        self._saved = None
-        self._training = False
+        self._reset_state()
         self.use_fused = True   # fused A->B->C branch kernel when (C, K, L) fits its LDS tile; else 3 stage kernels
         # fused branches on the bf16 matrix cores at fp32 accuracy (spectral_x3.hip: 16 or 8 lines per workgroup -- the library
         # picks 8 while the launch still fits one round of workgroups -- packed pre-split weights) for the axes the library
         # takes (C = 64, K <= 16); 17..32 modes go through the split-bf16 stage kernels
         self.use_x3 = True
-        self._last_plan = None      # the plan of the last forward pass (paired_last, infer_last, _saved_x3, ...)
-        self._dft_tabs = {}
         # feed-forward weight gradients of ALL layers as one launch after the backward loop (ffno_ffh_bwd_weights_partial_multi):
         # every layer keeps its own gradient buffer instead of the ping-pong pair; FF_WGRAD_ROUNDS x resident workgroups / L
         # slices per layer
@@ -274,7 +356,6 @@ class FFNOEngine:
         self.infer_self_range = True      # inference layers of axis length <= 64 scale every line from its own maximum (no range words)
         self.infer_stack_any_batch = False      # (see _stack_pays)
         self.infer_min_lines = None      # lines per axis pair from which the inference layer is used (None: more than 4 per CU)
-        self._issue_stream = None   # torch stream object the next launches go to (None = current stream)
         self.timer = None   # optional KernelTimer (bench.py): HIP-event timing of individual launches
         # fp16x2 packs: max |W| of what goes into them is folded at every n-th rebuild of the derived operands (0 = never) and
         # looked at one rebuild later -- with 1 (the default since round 4: three 3-us launches per step) an overflowing weight
@@ -296,6 +377,45 @@ class FFNOEngine:
         # memory cap of the deferred weight-gradient launch (2 L P C more words with lazy sums, 1.7 GB at the headline shape):
         # beyond it the engine keeps the ping-pong pair and per-layer launches
         self.ff_defer_max_bytes = int(env.get("FFNO_FF_DEFER_MAX_BYTES", 16 << 30))
+
+    def _reset_state(self):
+        """Every mutable private attribute, with the value of an engine nothing is bound to yet."""
+        self.params: Dict[str, torch.Tensor] = {}
+        self.device = None
+        self._bind_sig = None       # data pointers of the tensors bind() validated last
+        self._issue_stream = None   # torch stream object the next launches go to (None = current stream)
+        self._training = False      # the pass in flight draws dropout masks
+        self._drop_calls = 0        # training forwards so far: every one draws new masks
+        self._in_drop_seed = 0      # seed of the last pass's input-dropout mask (the backward pass regenerates it)
+        self._last_plan = None      # the plan of the last forward pass (paired_last, infer_last, _saved_x3, ...)
+        self._saved = None          # _Saved of the last forward(save_for_backward=True)
+        self.dx = None              # backward(need_dx=True): gradient with respect to the input
+        self.forecast_list = []     # use_fork: the per-layer head outputs of the last forward
+        self.infer_stack_last = False      # the last forward ran as the persistent inference launch
+        self._wr_count = 0          # weight-range check (_check_weight_range): rebuilds counted
+        self._wr_warned = False     # ... the small-weight warning was given
+        self._reset_device_state()
+
+    def _reset_device_state(self):
+        """The part of the state that lives on the device or was derived for it: dropped when the parameters move to another."""
+        self._ptr_sig = None        # what _refresh_pointers laid the views, descriptors and packs out for
+        self._prep_sig = None       # what _prepare_weights built the derived operands from (None: rebuild)
+        self._ws = None             # the current workspace ...
+        self._ws_key = None         # ... its key ...
+        self._ws_cache = {}         # ... among a few recent ones: train / validation / rollout batches alternate in a real run
+        self._tw: Dict[int, torch.Tensor] = {}      # twiddle tables by axis length
+        self._dft_tabs = {}         # DFT-fragment tables by (axis length, modes, direction); False: none for this shape
+        self._desc_dev = None       # weight-norm descriptor table ...
+        self._n_desc = 0            # ... its rows ...
+        self._max_rows = 0          # ... and the longest weight in it
+        self._fx_flat = None        # feed-forward operand packs, one buffer ...
+        self._fx_dev = None         # ... their descriptor table ...
+        self._n_fx = 0              # ... and its rows
+        self._fwpack = _lib.CachedTable()      # table of the Fourier-weight pack launch
+        self._x3pack = _lib.CachedTable()      # ... of the x3 pack launch
+        self._wr_word = None        # weight-range check: the device word ...
+        self._wr_late = _DeferredWord(self.device)      # ... the late look at it (max |W|) ...
+        self._wr_table = _lib.CachedTable()      # ... and the table of its amax launch
 
     def _bf16(self) -> bool:
         if self.storage not in ("fp32", "bf16"):
@@ -362,7 +482,7 @@ class FFNOEngine:
 
     def _branch(self, v, src, dst, resid, save, planes, acc, x3=False, fwd=True, rin=None, rout=None):
         """Branch descriptor; with fp16x2 packs the x3 kernel scales its spectrum tile from the range word of ``src``."""
-        fmt = int(getattr(v, "x3fmt", 1)) if (x3 and planes is not None and self._x3_h2()) else 0      # ffno.h FFNO_PLANES_*
+        fmt = int(v.x3fmt) if (x3 and planes is not None and self._x3_h2()) else 0      # ffno.h FFNO_PLANES_*
         dft = self._dft_frags(v.L, v.K, fwd) if fmt else None
         return _capi.FusedBranch(_p(src), _p(dst), resid, _p(save), _p(planes), _p(self._twiddle(v.L)), v.Bv, v.Mv, v.Nv, v.K,
                                  v.a01, acc, fmt, 0, rin if fmt else None, rout, self._st(), 0, _p(dft))      # (tile_lines 0: library's)
@@ -394,9 +514,6 @@ class FFNOEngine:
     def _rw(self, ws, kind: str, l: int):
         return ctypes.c_void_p(ws.RW.data_ptr() + 4 * (ws.rw_kinds[kind] * (self.L + 1) + l)) if self._ranged() else None
 
-    def _word(self, ws, kind: str, l: int):
-        return ctypes.c_void_p(ws.RW.data_ptr() + 4 * (ws.rw_kinds[kind] * (self.L + 1) + l))
-
     def _fw_words(self, ws, l0: int):
         """Range words of the tensors whose spectra the Fourier-weight-gradient launch contracts, from layer l0 on: the layer inputs
         (kind x) and the feed-forward data gradients (kind d) -- (x words, d words) as device pointers, or (None, None): then the
@@ -404,7 +521,7 @@ class FFNOEngine:
         run on fp16x2 packs (x3_mix_split), i.e. when every producer on the path records its maximum."""
         if not (self._x3_h2() and self._ranged() and self.spectral == "factorized" and self.use_x3):
             return None, None
-        return self._word(ws, "x", l0), self._word(ws, "d", l0)
+        return self._rw(ws, "x", l0), self._rw(ws, "d", l0)
 
     def _fold(self, t, word, st):
         """Producers that do not record their output maximum themselves: one more pass over the tensor."""
@@ -418,7 +535,9 @@ class FFNOEngine:
         return self.x3_mix_split == "fp16x2"
 
     def _ffx(self) -> bool:
-        return bool(not self.general_ff and _lib.get_lib().ffno_ffx_supported(self.C, self.H))
+        """The feed-forwards run on the split kernels (ffx.hip): whenever they are the fused two-linear shape -- __init__ admits
+        only the (width, hidden) pairs of _SUPPORTED_CH, which is those kernels' dispatch set (ffno_ffx_supported)."""
+        return not self.general_ff
 
     def _h2(self) -> bool:
         if self.ff_split not in ("fp16x2", "bf16x3"):
@@ -451,7 +570,7 @@ class FFNOEngine:
     def _k(self, name, fn, *args):
         """Enqueue one C-ABI call; with a timer attached, bracket it with HIP events on the launch stream."""
         t = self.timer
-        if t is not None and hasattr(t, "seen"):
+        if t is not None and hasattr(t, "seen"):      # (an optional method of the timer protocol, which is not engine state)
             t.seen(name, fn, args)          # bench.py: capture (entry point, arguments) for replay timing
         rc = fn(*args) if t is None else self._timed(name, fn, *args)
         if rc != 0:
@@ -471,7 +590,7 @@ class FFNOEngine:
         """Attach the parameter tensors (unique reference names -> fp32 contiguous device tensors)."""
         # the same storage as last time (a module re-binds its detached parameters on every forward): validated already
         sig = tuple(params[n].data_ptr() for n in self.param_names) if all(n in params for n in self.param_names) else None
-        if sig is not None and self.params and sig == getattr(self, "_bind_sig", None):
+        if sig is not None and self.params and sig == self._bind_sig:
             self.params = {n: params[n] for n in self.param_names}
             return
         missing = [n for n in self.param_names if n not in params]
@@ -503,8 +622,6 @@ class FFNOEngine:
         self.weff_flat = torch.empty(max(n_eff, 1), **f32)
         self.gweff_flat = torch.zeros(max(n_eff, 1), **f32)
         self.fold = torch.zeros(self.O * (self.C + 1), **f32)
-        n_ff = sum(l.rows * l.cols for p, l in self.linears.items() if "_ff." in p)
-        self.wt_flat = torch.empty(max(n_ff, 1), **f32)
         # mode-major weight planes: planes[set][w] = (wp, wpt), each 2*K_w*C*C floats
         plane_modes = [2 * self.K * self.K] if self.spectral == "plus" else list(self.Ks)   # plus: one joint (ky, kx') set
         self.planes = [[(torch.empty(2 * K * self.C * self.C, **f32), torch.empty(2 * K * self.C * self.C, **f32))
@@ -518,12 +635,7 @@ class FFNOEngine:
                     nb = int(lib.ffno_spectral_x3_pack_bytes(self.C, K))      # 0 = no split kernel for (C, K)
                     if nb:
                         self.xplanes[si][w] = tuple(torch.empty(nb // 4, dtype=torch.int32, device=dev) for _ in range(2))
-        self._x3pack_sig = None
-        self._prep_sig = None
-        self._ws_key = None
-        self._ws_cache = {}
-        self._tw = {}
-        self._dft_tabs = {}
+        self._reset_device_state()
 
     def grad_view(self, name: str) -> torch.Tensor:
         o = self._offsets[name]
@@ -550,22 +662,12 @@ class FFNOEngine:
                 lin.weff = self.params[lin.prefix + "weight"]
                 lin.gweff = self.grad_view(lin.prefix + "weight")
         self._n_desc = len(descs)
-        toff, tdescs = 0, []
-        for pfx, lin in self.linears.items():
-            if "_ff." not in pfx or self.general_ff:      # (the fp32 fused feed-forward's backward reads transposed weights)
-                continue
-            n = lin.rows * lin.cols
-            lin.wt = self.wt_flat[toff:toff + n].view(lin.cols, lin.rows)
-            toff += n
-            tdescs.append(_capi.TrDesc(lin.weff.data_ptr(), lin.wt.data_ptr(), lin.rows, lin.cols))
         # split-bf16 operand packs of every feed-forward block (include/ffno.h "packed"): forward A1/A2, backward A1/A2
         lib = _lib.get_lib()
         blocks = list(dict.fromkeys(self.ff_prefix + self.fc_prefix))
-        self._n_fx = 0
-        if lib.ffno_ffx_supported(self.C, self.H) and not self.general_ff:
+        if self._ffx():
             words = int((lib.ffno_ffh_pack_bytes if self._h2() else lib.ffno_ffx_pack_bytes)(self.C, self.H)) // 4
-            if getattr(self, "_fx_flat", None) is None or self._fx_flat.numel() != 4 * words * len(blocks) \
-                    or self._fx_flat.device != self.device:
+            if self._fx_flat is None or self._fx_flat.numel() != 4 * words * len(blocks):
                 self._fx_flat = torch.empty(4 * words * len(blocks), dtype=torch.int32, device=self.device)
             fdescs = []
             for bi, pfx in enumerate(blocks):
@@ -578,16 +680,9 @@ class FFNOEngine:
                                                    (l0.weff, C_, 1, 2)), pk):
                     fdescs.append(_capi.FxPackDesc(src.data_ptr(), dst.data_ptr(), sh, sc, ty, 0))
             self._n_fx = len(fdescs)
-            self._fx_dev = self._device_table(_capi.FxPackDesc, fdescs)
-        self._n_tr = len(tdescs)
-        self._tr_dev = self._device_table(_capi.TrDesc, tdescs)
+            self._fx_dev = _lib.device_table(_capi.FxPackDesc, fdescs, self.device)
         self._max_rows = max([l.rows for l in self.linears.values()])
-        self._desc_dev = self._device_table(_capi.WnDesc, descs) if descs else None
-
-    def _device_table(self, struct, items) -> torch.Tensor:
-        """A descriptor table (ctypes structs) as device bytes."""
-        arr = (struct * len(items))(*items)
-        return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+        self._desc_dev = _lib.device_table(_capi.WnDesc, descs, self.device) if descs else None
 
     def _twiddle(self, L: int) -> torch.Tensor:
         tw = self._tw.get(L)       # (this engine's memo of the package's one table cache: asked once per branch launch)
@@ -624,8 +719,8 @@ class FFNOEngine:
         key = self._workspace_key(B, S, save)
         if self._ws_key == key:
             return self._ws
-        cache = self.__dict__.setdefault("_ws_cache", {})   # a few recent geometries (train batch / validation batch /
-        if key in cache:                                     # rollout batch alternate in a real run): no re-allocation
+        cache = self._ws_cache
+        if key in cache:      # (no re-allocation)
             self._ws, self._ws_key = cache[key], key
             return self._ws
         lib = _lib.get_lib()
@@ -636,10 +731,9 @@ class FFNOEngine:
         f32 = dict(dtype=torch.float32, device=dev)
         act = dict(dtype=torch.bfloat16 if self._bf16() else torch.float32, device=dev)     # activation tensors of the layer stack
         ns = L if save else 1
-        ws = type("WS", (), {})()
+        ws = _Workspace()
         ws.P, ws.P_in, ws.Sp = P, P_in, Sp
         ws.views = self._views(B, Sp)
-        ws.padmap = ws.pm = None      # (pm: the argument the kernels take)
         if self.pad:
             s3 = (1,) * (3 - self.nd) + tuple(S)
             p3 = (1,) * (3 - self.nd) + tuple(Sp)
@@ -650,27 +744,25 @@ class FFNOEngine:
         ws.Y = torch.empty(P_in * O, **f32)
         ws.S = torch.empty(ns, P, C, **act)
         nv = len(ws.views)
-        ws.SXall = [torch.empty(ns, v.spec, **f32) for v in ws.views]      # forward spectra, per axis, layer-major
+        ws.SXall = [torch.empty(ns, v.spec, **f32) for v in ws.views]
         ws.SY = torch.empty(max(v.spec for v in ws.views), **f32)
-        ws.SD = torch.empty(max(v.spec for v in ws.views), **f32)    # scratch spectrum of the staged path
+        ws.SD = torch.empty(max(v.spec for v in ws.views), **f32)
         if self._conc():
-            ws.SD2 = torch.empty_like(ws.SD)                          # second branch of a paired STAGE launch
+            ws.SD2 = torch.empty_like(ws.SD)
             ws.SY2 = torch.empty_like(ws.SY)
-            ws.T = torch.empty(P, C, **act)                           # output of the second branch of a paired launch
+            ws.T = torch.empty(P, C, **act)
             if save:
-                ws.G1 = torch.empty(P, C, **act)                      # ... and of the second adjoint branch
+                ws.G1 = torch.empty(P, C, **act)
         if self.spectral == "plus":
             ws.chain = ws.views[0]
             ws.scr = ws.chain.scratch(lambda n: torch.empty(n, **f32))
         ws.mask_words = int(lib.ffno_ff_mask_words(P, H))
-        # range words, one per (tensor kind, layer): x = layer inputs, s = spectral-branch outputs (feed-forward inputs),
-        # g = running gradient (both buffers), d = feed-forward data gradients, t / f = LayerNorm / fork-head gradients
         ws.rw_kinds = {"x": 0, "s": 1, "g": 2, "d": 3, "t": 4, "f": 5}
         ws.RW = torch.zeros(len(ws.rw_kinds) * (L + 1), dtype=torch.int32, device=dev)
         if self.layer_norm:
-            ws.TL = torch.empty(ns, P, C, **f32)                     # feed-forward outputs before the LayerNorm
-            ws.LNS = torch.empty(ns, P, 2, **f32)                    # {mean, rstd} per pixel
-            if self.use_fork:            # the forecast feed-forwards end in their own LayerNorm (feedforward.py:18-19)
+            ws.TL = torch.empty(ns, P, C, **f32)
+            ws.LNS = torch.empty(ns, P, 2, **f32)
+            if self.use_fork:
                 ws.TLF = torch.empty(ns, P, C, **f32)
                 ws.LNSF = torch.empty(ns, P, 2, **f32)
             if save:
@@ -679,32 +771,24 @@ class FFNOEngine:
                 if self.use_fork:
                     ws.DTF = torch.empty(P, C, **f32)
         if self.use_fork:
-            ws.F = torch.empty(ns, P, C, **f32)                 # forecast_ff outputs f_l (inputs of the shared head)
-            ws.YL = torch.empty(L, P_in * O, **f32)             # per-layer head outputs (forecast_list)
+            ws.F = torch.empty(ns, P, C, **f32)
+            ws.YL = torch.empty(L, P_in * O, **f32)
         if self.general_ff:
-            # kept hidden activations of the general feed-forward path, per block kind / saved layer / hidden layer
             kinds = ["backcast"] + (["forecast"] if self.use_fork else [])
             ws.HG = {kind: [[torch.empty(P, H, **f32) for _ in range(self.n_ff - 1)] for _ in range(ns)] for kind in kinds}
             if save:
                 ws.DA = [torch.empty(P, H, **f32) for _ in range(2)]
                 ws.glpart = torch.empty(int(lib.ffno_glin_wgrad_partial_floats(P, H, H)), **f32)
-        fp32_ff = not self._ffx() and not self.general_ff      # the fp32 fused feed-forward keeps h / dh in HBM
         if save and self.use_fork:
-            ws.HF = torch.empty(ns, P, H, **f32) if fp32_ff else [None] * ns
             ws.MASKF = torch.zeros(ns, ws.mask_words, dtype=torch.int32, device=dev)
             ws.DSF = torch.empty(P, C, **f32)
             ws.GF = torch.empty(P, C, **f32)
             ws.redl = torch.empty(O * (C + 1), **f32)
         if save:
-            ws.Hbuf = torch.empty(ns, P, H, **f32) if fp32_ff else [None] * ns
             ws.MASK = torch.zeros(ns, ws.mask_words, dtype=torch.int32, device=dev)
-            ws.DH = [torch.empty(P, H, **f32) if fp32_ff else None for _ in range(2)]   # ping-pong pair (fp32 feed-forward: stored dh)
             ws.DS = torch.empty(P, C, **act)
-            # running gradient: a ping-pong pair -- or one buffer per layer when the weight-gradient launches are deferred to
-            # the end of the pass (they read every layer's summed gradient then)
             ws.defer_wgrad = bool(self.ff_wgrad_deferred and self._ffx() and self._h2() and self._ranged() and not self.share_fork
-                                  and not self.use_fork and not self.layer_norm and not self.general_ff
-                                  and (C, H) in ((64, 256), (32, 128)) and self.mode != "no-fourier")
+                                  and self._plain_layer and (C, H) in ((64, 256), (32, 128)) and self.mode != "no-fourier")
             if 2 * L * P * C * (2 if self._bf16() else 4) > int(self.ff_defer_max_bytes):      # (its memory cost)
                 ws.defer_wgrad = False
             ws.G = [torch.empty(P, C, **act) for _ in range(L + 1 if ws.defer_wgrad else 2)]
@@ -712,25 +796,24 @@ class FFNOEngine:
                 raise ValueError("ff_lazy_sums must be 's' or '0', got %r" % (self.ff_lazy_sums,))
             ws.lazy_sums = "s" if (ws.defer_wgrad and self.ff_lazy_sums == "s" and self._conc() and (C, H) == (64, 256)) else ""
             if ws.lazy_sums:
-                ws.TS = [torch.empty(P, C, **act) for _ in range(L)]         # second branch output of every layer
+                ws.TS = [torch.empty(P, C, **act) for _ in range(L)]
             ws.SDall = [torch.empty(L, v.spec, **f32) for v in ws.views] if self.mode == "full" else None
             ws.nsplit_ff = max(1, min(int(self.ff_wgrad_slices), (P + 127) // 128))
             cus = torch.cuda.get_device_properties(dev).multi_processor_count if dev.type == "cuda" else 256
             ws.nsplit_ffm = max(1, min(ws.nsplit_ff, (FF_WGRAD_ROUNDS * (3 if H <= 128 else 1) * cus) // L))
-            ws.wg_sig, ws.wg_table = None, None
+            ws.wg_table = _lib.CachedTable()
             ws.ffpart = torch.empty(int(lib.ffno_ff_wgrad_partial_floats(C, H, ws.nsplit_ff)), **f32)
-            # split-bf16 path with per-layer feed-forwards: every layer keeps its own slices and ONE batched launch
-            # reduces them all at the end of the backward pass (24 kernel boundaries less per step)
             ws.defer_reduce = bool(self._ffx() and not self.share_fork)
             if ws.defer_reduce:
                 njobs = L * (2 if self.use_fork else 1)
                 ws.ffparts = torch.empty(njobs, ws.ffpart.numel(), **f32)
-                ws.red_sig, ws.red_table = None, None
+                ws.red_table = _lib.CachedTable()
             ws.nsplit_fw = [max(1, min(max(1, FW_GRAD_WGS // v.K), (L * v.R + 63) // 64)) for v in ws.views]
             if self.spectral == "plus":
                 ws.nsplit_fw = [1]
             ws.fwpart = [[torch.empty(ws.nsplit_fw[w] * 2 * ws.views[w].modes * C * C, **f32) for w in range(nv)]
                          for _ in range(max(len(self._fw_sets), 1))]
+            ws.fwpart_multi, ws.fwgrad_tab, ws.fwgrad_sig = [None] * nv, [None] * nv, [None] * nv
             ws.nsplit_lift = max(1, min(1024, (P_in + 127) // 128))     # all slices co-resident (16 KB LDS per workgroup)
             ws.liftpart = torch.empty(ws.nsplit_lift * C * (self.Cin + 1), **f32)
             ws.nsplit_head = max(1, min(256, (P_in + 255) // 256))
@@ -774,7 +857,7 @@ class FFNOEngine:
                    tuple(x3fmt), self.use_x3, getattr(st, "value", st))
         except RuntimeError:      # inference tensors (created under torch.inference_mode()) have no version counter:
             sig = None            # nothing to compare -- the operands are rebuilt by every forward, as before round 3
-        if sig is not None and sig == getattr(self, "_prep_sig", None):
+        if sig is not None and sig == self._prep_sig:
             return
         self._prep_sig = sig
         if self._desc_dev is not None:
@@ -786,26 +869,15 @@ class FFNOEngine:
             self._k("fw2d_pack", lib.ffno_fw2d_pack, _p(self.params[names[0]]), _p(self.params[names[1]]),
                     _p(self.planes[i][0][0]), _p(self.planes[i][0][1]), self.C, self.K, st)
         if self.spectral != "plus" and self._fw_sets:      # every (weight set, axis) tensor in ONE launch
-            sig = tuple((self.params[n].data_ptr(), self.planes[i][w][0].data_ptr())
-                        for i, names in enumerate(self._fw_sets) for w, n in enumerate(names))
-            if sig != getattr(self, "_fwpack_sig", None):
-                descs = [_capi.FwPackDesc(self.params[n].data_ptr(), self.planes[i][w][0].data_ptr(),
-                                          self.planes[i][w][1].data_ptr(), self.Ks[w], int(self.spectral == "dct"))
-                         for i, names in enumerate(self._fw_sets) for w, n in enumerate(names)]
-                self._fwpack_dev = self._device_table(_capi.FwPackDesc, descs)
-                self._fwpack_sig, self._fwpack_n = sig, len(descs)
-            self._k("fw_pack", lib.ffno_fw_pack_batched, _p(self._fwpack_dev), self._fwpack_n, self.C, max(self.Ks), st)
+            rows = tuple((self.params[n].data_ptr(), self.planes[i][w][0].data_ptr(), self.planes[i][w][1].data_ptr(), self.Ks[w],
+                          int(self.spectral == "dct")) for i, names in enumerate(self._fw_sets) for w, n in enumerate(names))
+            self._k("fw_pack", lib.ffno_fw_pack_batched, _p(self._fwpack.get(_capi.FwPackDesc, rows, self.device)), len(rows),
+                    self.C, max(self.Ks), st)
             if self.use_x3 and any(x is not None for row in self.xplanes for x in row):
-                sig = tuple((self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), x3fmt[w]) for i, row in enumerate(self.xplanes)
-                            for w, xp in enumerate(row) if xp is not None for d in range(2))
-                if sig != self._x3pack_sig:
-                    descs = [_capi.X3PackDesc(self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), self.Ks[w], x3fmt[w])
-                             for i, row in enumerate(self.xplanes) for w, xp in enumerate(row) if xp is not None
-                             for d in range(2)]
-                    self._x3pack_dev = self._device_table(_capi.X3PackDesc, descs)
-                    self._x3pack_sig, self._x3pack_n = sig, len(descs)
-                    self._x3pack_maxk = max(d.K for d in descs)
-                self._k("fw_pack_x3", lib.ffno_spectral_x3_pack, _p(self._x3pack_dev), self._x3pack_n, self.C, self._x3pack_maxk, st)
+                rows = tuple((self.planes[i][w][d].data_ptr(), xp[d].data_ptr(), self.Ks[w], x3fmt[w])
+                             for i, row in enumerate(self.xplanes) for w, xp in enumerate(row) if xp is not None for d in range(2))
+                self._k("fw_pack_x3", lib.ffno_spectral_x3_pack, _p(self._x3pack.get(_capi.X3PackDesc, rows, self.device)),
+                        len(rows), self.C, max(r[2] for r in rows), st)
         o0, o1 = self.linears["out.0."], self.linears["out.1."]
         self._k("head_fold", lib.ffno_head_fold, _p(o0.weff), _p(self.params["out.0.bias"]), _p(o1.weff),
                 _p(self.params["out.1.bias"]), _p(self.fold), self.C, HEAD_DIM, self.O, st)
@@ -822,31 +894,25 @@ class FFNOEngine:
         fp16_ff, fp16_mix = self._ffx() and self._h2(), any(x3fmt)
         if every <= 0 or not (fp16_ff or fp16_mix):
             return
-        pend = self.__dict__.get("_wr_pending")
-        if pend is not None:
-            host, ev = pend
-            if ev is None or ev.query():
-                self._wr_pending = None
-                wmax = float(host.view(torch.float32)[0])
-                if 0.0 < wmax < 2.0 ** -9 and not self.__dict__.get("_wr_warned"):
-                    import warnings
-                    self._wr_warned = True
-                    warnings.warn(f"every weight that goes into the split-fp16 packs is below {wmax:.3g}: the packs keep a fixed "
-                                  f"absolute error of 2^-36 there, i.e. relative accuracy degrades as the weights shrink "
-                                  f"(1e-6 at 2e-5); ff_split / x3_mix_split = 'bf16x3' is exact at any magnitude", RuntimeWarning)
-                if not wmax < 65504.0:
-                    raise FloatingPointError(
-                        f"a weight of magnitude {wmax:.3g} does not fit the split-fp16 packs (|W| < 65504): set "
-                        f"engine.ff_split = engine.x3_mix_split = 'bf16x3' (FFNO_FF_SPLIT / FFNO_X3_MIX_SPLIT) -- any fp32 range")
-        self._wr_count = self.__dict__.get("_wr_count", 0) + 1
-        if (self._wr_count - 1) % every or self.__dict__.get("_wr_pending") is not None:
+        host = self._wr_late.take()
+        if host is not None:
+            wmax = float(host.view(torch.float32)[0])
+            if 0.0 < wmax < 2.0 ** -9 and not self._wr_warned:
+                import warnings
+                self._wr_warned = True
+                warnings.warn(f"every weight that goes into the split-fp16 packs is below {wmax:.3g}: the packs keep a fixed "
+                              f"absolute error of 2^-36 there, i.e. relative accuracy degrades as the weights shrink "
+                              f"(1e-6 at 2e-5); ff_split / x3_mix_split = 'bf16x3' is exact at any magnitude", RuntimeWarning)
+            if not wmax < 65504.0:
+                raise FloatingPointError(
+                    f"a weight of magnitude {wmax:.3g} does not fit the split-fp16 packs (|W| < 65504): set "
+                    f"engine.ff_split = engine.x3_mix_split = 'bf16x3' (FFNO_FF_SPLIT / FFNO_X3_MIX_SPLIT) -- any fp32 range")
+        self._wr_count += 1
+        if (self._wr_count - 1) % every or self._wr_late.pending:
             return
         lib = _lib.get_lib()
-        if self.__dict__.get("_wr_word") is None or self._wr_word.device != self.device:
+        if self._wr_word is None:
             self._wr_word = torch.zeros(1, dtype=torch.int32, device=self.device)
-            self._wr_host = torch.zeros(1, dtype=torch.int32)
-            if self.device.type == "cuda":
-                self._wr_host = self._wr_host.pin_memory()
         self._wr_word.zero_()
         srcs = []
         if fp16_ff:
@@ -858,19 +924,10 @@ class FFNOEngine:
             srcs += [self.params[n] for names in self._fw_sets for n in names]
         # ONE launch for all of them (per-layer Fourier weights are 2-3 tensors per layer: the airfoil model issued 49 of these
         # 4-us launches per step until round 5); the descriptor table is rebuilt when a tensor moved
-        sig = tuple((t.data_ptr(), t.numel()) for t in srcs)
-        if sig != self.__dict__.get("_wr_sig"):
-            self._wr_table = self._device_table(_capi.AmaxDesc, [_capi.AmaxDesc(ptr, n) for ptr, n in sig])
-            self._wr_sig = sig
-        self._k("amax", lib.ffno_amax_batched, _p(self._wr_table), len(sig), max(n for _, n in sig), _p(self._wr_word), st)
-        ev = None
-        if self.device.type == "cuda":
-            self._wr_host.copy_(self._wr_word, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        else:
-            self._wr_host.copy_(self._wr_word)
-        self._wr_pending = (self._wr_host, ev)
+        rows = tuple((t.data_ptr(), t.numel()) for t in srcs)
+        self._k("amax", lib.ffno_amax_batched, _p(self._wr_table.get(_capi.AmaxDesc, rows, self.device)), len(rows),
+                max(n for _, n in rows), _p(self._wr_word), st)
+        self._wr_late.post(self._wr_word)
 
     def _ff_weights(self, l, prefixes=None):
         """(linear 0, linear 1, bias 0, bias 1) of layer l's backcast (or, prefixes = fc_prefix, forecast) feed-forward."""
@@ -878,47 +935,22 @@ class FFNOEngine:
         l0, l1 = self.linears[fp + "layers.0.0."], self.linears[fp + "layers.1.0."]
         return l0, l1, self.params[fp + "layers.0.0.bias"], self.params[fp + "layers.1.0.bias"]
 
-    # ---- feed-forward dispatch: split-bf16 kernels (ffx.hip) or the fp32-MFMA kernels (ff.hip) ---------------------
-    def _ff_fwd(self, s, resid, l0, l1, b0, b1, out, hbuf, mask, P, st, rin=None, rout=None):
+    def _ff_bwd_weights(self, ws, s, s2, g, l0, l1, b0, gb0, gb1, accumulate, P, st, rs=None, rg=None):
+        """Weight gradients of one two-linear feed-forward block (``s2``: second addend of s with lazy input sums, else None)."""
         lib = _lib.get_lib()
-        if self._ffx():
-            self._ffs_fwd2(s, None, None, resid, l0, b0, b1, out, mask, P, st, rin, rout)
-        else:
-            self._k("ff_fwd", lib.ffno_ff_fwd, _p(s), _p(resid), _p(l0.weff), _p(b0), _p(l1.weff), _p(b1), _p(out),
-                    _p(hbuf), _p(mask), P, self.C, self.H, st)
-            self._fold(out, rout, st)
-
-    def _ff_bwd_data(self, g, mask, l0, l1, dh, ds, P, st, rin=None, rout=None):
-        lib = _lib.get_lib()
-        if self._ffx():
-            self._ffs_bwd2(g, None, None, mask, l0, ds, P, st, rin, rout)
-        else:
-            self._k("ff_bwd_data", lib.ffno_ff_bwd_data, _p(g), _p(mask), _p(l0.wt), _p(l1.wt), _p(dh), _p(ds), P,
-                    self.C, self.H, st)
-            self._fold(ds, rout, st)
-
-    def _ff_bwd_weights(self, ws, s, g, hbuf, dh, l0, l1, b0, gb0, gb1, accumulate, P, st, rs=None, rg=None):
-        lib = _lib.get_lib()
-        C, H = self.C, self.H
-        if self._ffx() and ws.defer_reduce:
+        if ws.defer_reduce:
             assert not accumulate
             part = ws.ffparts[len(ws.red_jobs)]
-            if getattr(ws, "wg_jobs", None) is not None:
-                s2 = getattr(self, "_wg_second", None)      # second addend of s (lazy input sums)
+            if ws.wg_jobs is not None:
                 ws.wg_jobs.append((s.data_ptr(), g.data_ptr(), l0.fx[0].data_ptr(), b0.data_ptr(), l0.fx[2].data_ptr(),
                                    part.data_ptr(), rs.value, rg.value, s2.data_ptr() if s2 is not None else 0, 0))
             else:
                 self._ffs_wgrad(s, g, l0, b0, part, P, ws.nsplit_ff, st, rs, rg)
             ws.red_jobs.append((part.data_ptr(), l0.gweff.data_ptr(), l1.gweff.data_ptr(), gb0.data_ptr(), gb1.data_ptr()))
-        elif self._ffx():
+        else:
             self._ffs_wgrad(s, g, l0, b0, ws.ffpart, P, ws.nsplit_ff, st, rs, rg)
             self._k("ff_bwd_weights_reduce", lib.ffno_ffx_bwd_weights_reduce, _p(ws.ffpart), _p(l0.gweff), _p(l1.gweff),
-                    _p(gb0), _p(gb1), C, H, ws.nsplit_ff, accumulate, st)
-        else:
-            self._k("ff_bwd_weights_partial", lib.ffno_ff_bwd_weights_partial, _p(s), _p(g), _p(hbuf), _p(dh),
-                    _p(ws.ffpart), P, C, H, ws.nsplit_ff, st)
-            self._k("ff_bwd_weights_reduce", lib.ffno_ff_bwd_weights_reduce, _p(ws.ffpart), _p(l0.gweff), _p(l1.gweff),
-                    _p(gb0), _p(gb1), C, H, ws.nsplit_ff, accumulate, st)
+                    _p(gb0), _p(gb1), self.C, self.H, ws.nsplit_ff, accumulate, st)
 
     # ---- the GENERAL feed-forward path (n_ff_layers != 2 or dropout > 0): one glin kernel per linear layer ------------------
     def _drop_args(self, layer: int, kind: str, k: int):
@@ -994,13 +1026,12 @@ class FFNOEngine:
         if not (self.use_infer_layer and conc and pair is not None and not singles and x3pair and fused[pair[0]]):
             return False
         if not (self.nd == 2 and self.mode == "full" and self.spectral == "factorized" and self._ffx() and self._h2() and self._x3_h2()
-                and not self._bf16() and not self.use_fork and not self.layer_norm and not self.general_ff
-                and (self.C, self.H) == (64, 256)):
+                and not self._bf16() and self._plain_layer and (self.C, self.H) == (64, 256)):
             return False
         va, vb = ws.views[pair[0]], ws.views[pair[1]]
         if {va.a01, vb.a01} != {0, 1} or (va.Bv, va.Mv, va.Nv) != (vb.Bv, vb.Mv, vb.Nv):
             return False
-        if any(getattr(v, "x3fmt", 0) != 1 for v in (va, vb)):
+        if any(v.x3fmt != 1 for v in (va, vb)):
             return False
         row, col = (va, vb) if va.a01 == 0 else (vb, va)
         lib = _lib.get_lib()
@@ -1039,23 +1070,16 @@ class FFNOEngine:
             return False
         if not self._stack_pays(va.Bv):
             return False
-        pend = getattr(ws, "stack_pending", None)
-        if pend is not None:      # the error word of the PREVIOUS persistent launch on this workspace (copied without synchronising)
-            host, ev = pend
-            if ev is None or ev.query():
-                ws.stack_pending = None
-                if int(host[0]) != 0:
-                    self.use_infer_stack = False
-                    raise RuntimeError("ffno_infer_stack: the previous forward pass reported a workgroup without a group or a barrier "
-                                       "time-out (error word %d): its result was invalid; the persistent launch is now off for this "
-                                       "engine (engine.use_infer_stack)" % int(host[0]))
-        if getattr(ws, "stack_sync", None) is None:
+        if ws.stack_sync is None:
             n = int(lib.ffno_infer_stack_sync_words(va.Bv))
             ws.stack_sync = torch.zeros(n, dtype=torch.int32, device=self.device)
-            ws.stack_host = torch.zeros(1, dtype=torch.int32)
-            if self.device.type == "cuda":
-                ws.stack_host = ws.stack_host.pin_memory()
-            ws.stack_checked = False
+            ws.stack_late = _DeferredWord(self.device)
+        host = ws.stack_late.take()      # the error word of a PREVIOUS persistent launch on this workspace (copied without synchronising)
+        if host is not None and int(host[0]) != 0:
+            self.use_infer_stack = False
+            raise RuntimeError("ffno_infer_stack: the previous forward pass reported a workgroup without a group or a barrier "
+                               "time-out (error word %d): its result was invalid; the persistent launch is now off for this "
+                               "engine (engine.use_infer_stack)" % int(host[0]))
         ba = self._branch(va, ws.X, ws.MIX[0], None, None, None, 0, True, True, None, None)
         bb = self._branch(vb, ws.X, ws.MIX[1], None, None, None, 0, True, True, None, None)
         for br, v in ((ba, va), (bb, vb)):
@@ -1074,7 +1098,7 @@ class FFNOEngine:
             self.use_infer_stack = False
             return False
         err_word = ws.stack_sync[-1:]
-        ws.stack_calls = getattr(ws, "stack_calls", 0) + 1
+        ws.stack_calls += 1
         if not ws.stack_checked:
             # first persistent launch on this workspace: look at its error word before trusting the path
             ws.stack_checked = True
@@ -1084,13 +1108,10 @@ class FFNOEngine:
                 warnings.warn("ffno_infer_stack reported a placement / barrier error on this device: using the per-layer launches",
                               RuntimeWarning)
                 raise _StackRetry()
-        elif self.device.type == "cuda" and getattr(ws, "stack_pending", None) is None and ws.stack_calls % 16 == 0:
+        elif self.device.type == "cuda" and not ws.stack_late.pending and ws.stack_calls % 16 == 0:
             # (every 16th launch: the 4-byte copy is a launch of its own; an error after the first checked launch would be a
             #  hardware / scheduling anomaly -- it is reported a few passes late, but it is reported)
-            ws.stack_host.copy_(err_word, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            ws.stack_pending = (ws.stack_host, ev)
+            ws.stack_late.post(err_word)
         return True
 
     def _spectral(self, name, ws, v: _View, src, dst, resid, save, planes, fwd: bool, accumulate: int, fused: bool, st,
@@ -1225,12 +1246,11 @@ class FFNOEngine:
                 lib.ffno_spectral_x3_staged_supported(C, ws.views[w].K, ws.views[w].L)
                 and (not full or self.xplanes[0][w] is not None) for w in pair)
                 and 4 * C * max(v.Bv * v.Mv * v.Nv for v in ws.views) < 2 ** 32)
-        layer_calls = bool(self.use_layer_calls and self.timer is None and conc and fused[pair[0]] and not self.use_fork
-                           and not self.layer_norm)
-        bwd_layer_calls = bool(self.use_layer_calls and conc and fused[pair[0]] and not singles and not self.use_fork
-                               and getattr(ws, "defer_reduce", False) and self.mode != "no-fourier" and not self.layer_norm)
+        layer_calls = bool(self.use_layer_calls and self.timer is None and conc and fused[pair[0]] and self._plain_layer)
+        bwd_layer_calls = bool(self.use_layer_calls and conc and fused[pair[0]] and not singles and self._plain_layer
+                               and ws.defer_reduce and self.mode != "no-fourier")
         infer = bool(not save and self._infer_ok(ws, conc, pair, singles, x3pair, fused))
-        if infer and getattr(ws, "MIX", None) is None:
+        if infer and ws.MIX is None:
             ws.MIX = [torch.empty(int(lib.ffno_infer_mix_bytes(C, ws.views[w].K, ws.views[w].R)) // 4, dtype=torch.int32,
                                   device=self.device) for w in pair]
         # self-ranged inference layers (axis lengths <= 64: ffno.h FFNO_BRANCH_SELF_RANGE): the first kernel scales every line from its
@@ -1238,11 +1258,10 @@ class FFNOEngine:
         infer_sr = bool(infer and self.infer_self_range and all(ws.views[w].L <= 64 for w in pair))
         # both branch outputs of every layer are kept and the feed-forward does not write their sum (the deferred weight-gradient
         # launch forms it)
-        lazy = bool(save and conc and getattr(ws, "lazy_sums", ""))
+        lazy = bool(save and conc and ws.lazy_sums)
         bf16 = self._bf16()
-        if bf16 and not (all(fused) and all(x3) and self._h2() and self._x3_h2() and self._ffx() and self.spectral == "factorized"
-                         and (C, H) in ((64, 256), (32, 128)) and full and not self.use_fork and not self.layer_norm
-                         and self.dropout == 0.0 and self.in_dropout == 0.0):
+        if bf16 and not (all(fused) and all(x3) and self._h2() and self._x3_h2() and self._plain_layer and self.spectral == "factorized"
+                         and (C, H) in ((64, 256), (32, 128)) and full and self.dropout == 0.0 and self.in_dropout == 0.0):
             raise NotImplementedError(
                 "storage='bf16' covers the fused split-kernel path of the factorized operators (2-D grids / meshes and the 3-D mesh: "
                 "width 64 with up to 64 modes or width 32 with up to 16, factor 4, mode='full', fp16x2 splits, 2-layer feed-forward "
@@ -1343,16 +1362,13 @@ class FFNOEngine:
         ff_out = ws.TL[sv] if self.layer_norm else (ws.Blast if last else ws.X)
         ff_res = None if (self.layer_norm or last) else ws.X
         ff_rout = None if self.layer_norm else rxn     # (LayerNorm: the next layer's input is the normalised tensor)
-        if plan.conc:
-            self._ffs_fwd2(s_l, t_l, s_l if (save and not plan.lazy) else None, ff_res, l0, b0, b1, ff_out,
-                           ws.MASK[sv] if save else None, P, st, rs_, ff_rout)
-        elif self.use_fork and last:          # with fork heads the last layer's backcast only feeds the dead x_L
+        if self.use_fork and last:            # with fork heads the last layer's backcast only feeds the dead x_L
             pass
         elif self.general_ff:
             self._ffg_fwd(ws, self.ff_prefix[l], "backcast", l, sv, s_l, ff_res, ff_out, P, st, ff_rout)
-        else:
-            self._ff_fwd(s_l, ff_res, l0, l1, b0, b1, ff_out, ws.Hbuf[sv] if save else None, ws.MASK[sv] if save else None, P, st,
-                         rs_, ff_rout)
+        else:      # (a paired launch left the second branch in t_l: the chain kernel adds it, and stores the sum unless it is lazy)
+            self._ffs_fwd2(s_l, t_l, s_l if (plan.conc and save and not plan.lazy) else None, ff_res, l0, b0, b1, ff_out,
+                           ws.MASK[sv] if save else None, P, st, rs_, ff_rout)
         if self.layer_norm and not (self.use_fork and last):
             ln = self.ff_prefix[l] + f"layers.{self.n_ff - 1}.3."
             self._k("layernorm_fwd", lib.ffno_layernorm_fwd, _p(ws.TL[sv]), _p(self.params[ln + "weight"]),
@@ -1366,8 +1382,7 @@ class FFNOEngine:
             if self.general_ff:
                 self._ffg_fwd(ws, self.fc_prefix[l], "forecast", l, sv, s_l, None, f_raw, P, st)
             else:
-                self._ff_fwd(s_l, None, c0, c1, cb0, cb1, f_raw, ws.HF[sv] if save else None, ws.MASKF[sv] if save else None, P, st,
-                             rs_, None)
+                self._ffs_fwd2(s_l, None, None, None, c0, cb0, cb1, f_raw, ws.MASKF[sv] if save else None, P, st, rs_, None)
             if self.layer_norm:
                 ln = self.fc_prefix[l] + f"layers.{self.n_ff - 1}.3."
                 self._k("layernorm_fwd", lib.ffno_layernorm_fwd, _p(f_raw), _p(self.params[ln + "weight"]),
@@ -1387,7 +1402,7 @@ class FFNOEngine:
             # the backward's range words (g: running gradient, d: feed-forward data gradients, t / f: LayerNorm / fork heads):
             # every fp16x2 kernel of the pass scales its operands from the maximum its producer recorded -- per layer, on the
             # device, so no growth or decay of the gradient through the layers can leave the half format's range
-            if not getattr(ws, "rw_bwd_clean", False):      # (a second backward pass over the same forward)
+            if not ws.rw_bwd_clean:      # (a second backward pass over the same forward)
                 ws.RW[2 * (L + 1):].zero_()
             ws.rw_bwd_clean = False
         self._head_bwd(ws, plan, gy, st)
@@ -1395,7 +1410,7 @@ class FFNOEngine:
         # deferred weight-gradient launch: (s, summed gradient, packs, words, slices) of every layer, one launch after the loop
         # (paired launches or not: the airfoil mesh -- a 32-mode axis beside a 16-mode one, two launches per layer -- ran 24 per-layer
         #  weight-gradient launches of 56 us until round 5)
-        ws.wg_jobs = [] if getattr(ws, "defer_wgrad", False) else None
+        ws.wg_jobs = [] if ws.defer_wgrad else None
         if plan.lazy and ws.wg_jobs is None:
             raise RuntimeError("the forward pass left the feed-forward input sums to a deferred weight-gradient launch that this "
                                "backward pass cannot run")
@@ -1434,8 +1449,6 @@ class FFNOEngine:
                     _p(ws.G[0]), _p(ws.headpart), _p(ws.red), ws.P_in, C, self.O, ws.nsplit_head, pm, self._rw(ws, "g", self.L - 1), st)
         self._k("head_param_grads", lib.ffno_head_param_grads, _p(ws.red), _p(o0.weff), _p(self.params["out.0.bias"]),
                 _p(o1.weff), _p(o0.gweff), _p(gv("out.0.bias")), _p(o1.gweff), _p(gv("out.1.bias")), C, HEAD_DIM, self.O, 0, st)
-        if not self._ffx() and self._n_tr:
-            self._k("transpose_batched", lib.ffno_transpose_batched, _p(self._tr_dev), self._n_tr, max(C, self.H), max(C, self.H), st)
 
     def _bwd_forecast(self, ws, l: int, words, ff_seen, st):
         """Fork heads: the forecast feed-forward of layer l (after its LayerNorm) -> its part of dL/ds."""
@@ -1455,9 +1468,8 @@ class FFNOEngine:
         if self.general_ff:
             self._ffg_bwd(ws, fc, "forecast", l, ws.S[l], g_fc, ds_f, int(fc in ff_seen), P, st, rd)
         else:
-            dh = ws.DH[l & 1]
-            self._ff_bwd_data(g_fc, ws.MASKF[l], c0, c1, dh, ds_f, P, st, rf, rd)
-            self._ff_bwd_weights(ws, ws.S[l], g_fc, ws.HF[l], dh, c0, c1, self.params[fc + "layers.0.0.bias"],
+            self._ffs_bwd2(g_fc, None, None, ws.MASKF[l], c0, ds_f, P, st, rf, rd)
+            self._ff_bwd_weights(ws, ws.S[l], None, g_fc, c0, c1, self.params[fc + "layers.0.0.bias"],
                                  gv(fc + "layers.0.0.bias"), gv(fc + "layers.1.0.bias"), int(fc in ff_seen), P, st, rs_, rf)
         ff_seen.add(fc)
 
@@ -1514,7 +1526,7 @@ class FFNOEngine:
     def _bwd_layer_launches(self, ws, plan: _Plan, l: int, cur: int, have_g1: bool, words, ff_seen, st) -> bool:
         """Layer l backward as launches: LayerNorm, feed-forward (data, weights), adjoint branches.  -> G1 holds a part of g_out."""
         lib, C, P, gv, fp, last = _lib.get_lib(), self.C, ws.P, self.grad_view, self.ff_prefix[l], l == self.L - 1
-        g_in, g_out, g1, dh = ws.G[cur], ws.G[(cur + 1) % len(ws.G)], getattr(ws, "G1", None), ws.DH[l & 1]
+        g_in, g_out, g1 = ws.G[cur], ws.G[(cur + 1) % len(ws.G)], ws.G1
         rg, rs_, rd, rgo, full = *words, self.mode == "full"
         l0, l1, _, _ = self._ff_weights(l)
         g_ff = g_in       # gradient w.r.t. the feed-forward output
@@ -1528,18 +1540,13 @@ class FFNOEngine:
             g_ff = ws.DT
             rg = self._rw(ws, "t", l)
             self._fold(ws.DT, rg, st)
-        if plan.conc:
-            # g_in (+)= G1 while it is staged; the sum is stored back for the weight gradient and the residual path
-            two = bool(have_g1 and not self.layer_norm)
-            self._ffs_bwd2(g_ff, g1 if two else None, g_ff if two else None, ws.MASK[l], l0, ws.DS, P, st, rg, rd)
-            self._wg_second = ws.TS[l] if plan.lazy else None
-        elif self.general_ff:
+        if self.general_ff:
             self._ffg_bwd(ws, fp, "backcast", l, ws.S[l], g_ff, ws.DS, int(fp in ff_seen), P, st, rd)
         else:
-            self._ff_bwd_data(g_ff, ws.MASK[l], l0, l1, dh, ws.DS, P, st, rg, rd)
-            self._wg_second = None
-        if not self.general_ff:
-            self._ff_bwd_weights(ws, ws.S[l], g_ff, ws.Hbuf[l], dh, l0, l1, self.params[fp + "layers.0.0.bias"],
+            # paired launches: g_in (+)= G1 while it is staged; the sum is stored back for the weight gradient and the residual path
+            two = bool(plan.conc and have_g1 and not self.layer_norm)
+            self._ffs_bwd2(g_ff, g1 if two else None, g_ff if two else None, ws.MASK[l], l0, ws.DS, P, st, rg, rd)
+            self._ff_bwd_weights(ws, ws.S[l], ws.TS[l] if plan.lazy else None, g_ff, l0, l1, self.params[fp + "layers.0.0.bias"],
                                  gv(fp + "layers.0.0.bias"), gv(fp + "layers.1.0.bias"), int(fp in ff_seen), P, st, rs_, rg)
         ff_seen.add(fp)
         if self.use_fork:
@@ -1582,18 +1589,12 @@ class FFNOEngine:
         nsl = ws.nsplit_ff
         if ws.wg_jobs:
             nsl = ws.nsplit_ffm
-            sig = tuple(ws.wg_jobs)
-            if sig != ws.wg_sig:      # (a HOST table: the library copies it into the kernel arguments at enqueue)
-                ws.wg_table = (_capi.FfWgDesc * len(sig))(*[_capi.FfWgDesc(*j) for j in sig])
-                ws.wg_sig = sig
-            self._k("ff_bwd_weights_partial", lib.ffno_ffh_bwd_weights_partial_multi, ws.wg_table, len(sig), P, C, H, nsl,
+            table = ws.wg_table.get(_capi.FfWgDesc, tuple(ws.wg_jobs))      # (a HOST table)
+            self._k("ff_bwd_weights_partial", lib.ffno_ffh_bwd_weights_partial_multi, table, len(table), P, C, H, nsl,
                     self._st(), int(plan.lazy), st)
-        if getattr(ws, "defer_reduce", False) and ws.red_jobs:
-            sig = tuple(ws.red_jobs)
-            if sig != ws.red_sig:       # pointers only change when parameters are re-bound or the workspace is rebuilt
-                ws.red_table = self._device_table(_capi.FxRedDesc, [_capi.FxRedDesc(*j) for j in sig])
-                ws.red_sig = sig
-            self._k("ff_bwd_weights_reduce", lib.ffno_ffx_bwd_weights_reduce_batched, _p(ws.red_table), len(sig), C, H,
+        if ws.defer_reduce and ws.red_jobs:
+            table = ws.red_table.get(_capi.FxRedDesc, tuple(ws.red_jobs), self.device)
+            self._k("ff_bwd_weights_reduce", lib.ffno_ffx_bwd_weights_reduce_batched, _p(table), len(ws.red_jobs), C, H,
                     nsl, st)
         g_fin = ws.G[cur]
         lin_in = self.linears["in_proj."]
@@ -1619,12 +1620,10 @@ class FFNOEngine:
                 # slices for the reduce launch to read back; ~512 workgroups in all are enough
                 nsf = max(1, min(-(-FW_GRAD_WGS // (v.K * L)), (v.R + 63) // 64))
                 pstride = nsf * 2 * v.K * C * C
-                if getattr(ws, "fwpart_multi", None) is None:
-                    ws.fwpart_multi, ws.fwgrad_tab, ws.fwgrad_sig = {}, {}, {}
-                if w not in ws.fwpart_multi or ws.fwpart_multi[w].numel() != L * pstride:
+                if ws.fwpart_multi[w] is None or ws.fwpart_multi[w].numel() != L * pstride:
                     ws.fwpart_multi[w] = torch.empty(L * pstride, dtype=torch.float32, device=self.device)
                 ptrs = tuple(gv(self._fw_sets[l][w]).data_ptr() for l in range(L))
-                if ws.fwgrad_sig.get(w) != ptrs:
+                if ws.fwgrad_sig[w] != ptrs:      # (a plain int64 tensor, not a descriptor table: as it was)
                     ws.fwgrad_tab[w] = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
                     ws.fwgrad_sig[w] = ptrs
                 xw, dw = self._fw_words(ws, 0)
@@ -1662,12 +1661,10 @@ class FFNOEngine:
             # a LIST per block: one active set per hidden activation; with dropout a dropped unit counts as inactive
             return {(kind, l): [(h > 0).to(torch.uint8) for h in ws.HG[kind][l]] for kind in ws.HG for l in range(self.L)
                     if not (kind == "backcast" and self.use_fork and l == self.L - 1)}
-        if not self._ffx():
-            raise RuntimeError("relu_active_sets() needs a preceding forward(save_for_backward=True) on the ffx path")
         lib = _lib.get_lib()
         st = _lib.current_stream(self.device)
         out = {}
-        for kind, masks in (("backcast", ws.MASK), ("forecast", getattr(ws, "MASKF", None))):
+        for kind, masks in (("backcast", ws.MASK), ("forecast", ws.MASKF)):
             if masks is None:
                 continue
             for l in range(self.L):

@@ -157,10 +157,7 @@ class ZongyiEngine:
                 R, Cc, inner, Rp, Cp = self._pad_geom[n]
                 descs.append(_capi.PadDesc(plain_of(n).data_ptr(), self._pp(n, padded_buf).data_ptr(), R, Cc, inner, Cp))
             self._n_pad = len(descs)
-            if not descs:
-                return None
-            arr = (_capi.PadDesc * len(descs))(*descs)
-            return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+            return _lib.device_table(_capi.PadDesc, descs, self.device) if descs else None
 
         self._ptab = table(lambda n: self.params[n], self.ppad)
         self._gtab = table(self.grad_view, self.gpad)

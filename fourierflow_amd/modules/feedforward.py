@@ -1,7 +1,7 @@
 """FeedForward -- mirror of ``fourierflow.modules.feedforward.FeedForward``
 (fourierflow/modules/feedforward.py:6-24).  Same constructor and state-dict keys
 (``layers.{i}.0.{weight_g,weight_v,bias}``); forward = one fused HIP kernel
-(GEMM1 + bias + ReLU + GEMM2 + bias, ffno_ff_fwd).
+(GEMM1 + bias + ReLU + GEMM2 + bias, ffno_ff_fwd: the fp32-MFMA kernel; inside an operator block the engine runs ffx.hip's instead).
 
 The fused kernels implement n_layers == 2, dropout == 0 (every shipped experiment config); a block that owns an engine with the
 GENERAL feed-forward path (one glin kernel per linear layer, regenerated dropout masks: csrc/glin.hip) also takes n_layers >= 2 and

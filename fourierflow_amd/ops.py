@@ -106,11 +106,11 @@ class _WeightNormFn(torch.autograd.Function):
     @staticmethod
     def _run(g, v, w, dw, dg, dv, bwd):
         lib = _lib.get_lib()
-        desc = (_capi.WnDesc * 1)(_capi.WnDesc(g.data_ptr(), v.data_ptr(), w.data_ptr() if w is not None else 0,
-                                               dw.data_ptr() if dw is not None else 0,
-                                               dg.data_ptr() if dg is not None else 0,
-                                               dv.data_ptr() if dv is not None else 0, v.shape[0], v.shape[1]))
-        dev = torch.from_numpy(np.frombuffer(bytes(desc), dtype=np.uint8).copy()).to(v.device)
+        desc = _capi.WnDesc(g.data_ptr(), v.data_ptr(), w.data_ptr() if w is not None else 0,
+                            dw.data_ptr() if dw is not None else 0,
+                            dg.data_ptr() if dg is not None else 0,
+                            dv.data_ptr() if dv is not None else 0, v.shape[0], v.shape[1])
+        dev = _lib.device_table(_capi.WnDesc, [desc], v.device)
         fn = lib.ffno_weightnorm_bwd if bwd else lib.ffno_weightnorm_fwd
         _capi.check(fn(_p(dev), 1, v.shape[0], _lib.current_stream(v.device)), "weightnorm")
         return dev  # keep alive until enqueued work is ordered behind later work on the same stream

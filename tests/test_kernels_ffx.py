@@ -145,6 +145,14 @@ def test_ffx_rejects_unsupported_shapes(be):
     assert be.lib.ffno_ffx_fwd(None, None, p(z), p(z), p(z), p(z), p(z), None, 1, 64, 256, None) == -1
 
 
+def test_ffx_takes_every_shape_the_engine_admits(be):
+    """FFNOEngine has no other feed-forward path for the two-linear shape: `_ffx()` rests on this."""
+    from fourierflow_amd import engine
+    assert engine._SUPPORTED_CH
+    for C, H in sorted(engine._SUPPORTED_CH):
+        assert be.lib.ffno_ffx_supported(C, H) == 1, (C, H)
+
+
 def test_ffx_two_input_variants_equal_the_presummed_call(be):
     """ffno_ffx_fwd2 / ffno_ffx_bwd_data2 (input = sum of the two spectral branch buffers, optionally stored back) are
     bit-identical to summing first and calling the one-input entry points."""
