@@ -264,7 +264,8 @@ SIGNATURES = {
     "ffno_markov_traj_ws_floats": (SZ, [I, I, I, I]),
     "ffno_markov_traj_step": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "ffno_markov_traj_metrics": (I, [P, P, I, I, I, I, F, P]),
-    "ffno_adamw_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
+    "ffno_markov_pairs": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "ffno_adamw_flat":(I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_adam_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_axpy": (I, [P, P, F, SZ, P]),
     "ffno_nudft_supported": (I, [I, I, I]),

@@ -12,7 +12,9 @@ interpolations), Lightning (the routines run their own fused step), wandb (one J
 and the dataset builders.  Batches therefore come from ``--data FILE.npz`` (arrays named like
 the builder's batches: ``x``/``y`` [, ``f``, ``mu``] for the Markov and mesh routines, ``data`` for the rollout routine;
 for the Markov routine a file with ``data`` [n, M, N, T] [, ``times``, ``f``, ``mu``, ``corr_data``] is a TRAJECTORY file, what
-its validation / test loaders deliver: `test --data` and `train --valid-data` run the autoregressive metrics on it;
+its validation / test loaders deliver: `test --data` and `train --valid-data` run the autoregressive metrics on it, and
+`train --data` with any of ``--pair-mode --pair-stride --epochs --no-shuffle --drop-last`` draws shuffled one-step pairs from it
+on the device (builders/markov_data.py; without one of these options a trajectory training file is refused);
 ``xy``/``rr``/``sigma`` for the point-cloud routine; first axis = samples) or, without it, are synthetic N(0,1) fields of the
 configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless ``--size``, ``rr`` [B, 42], ``sigma`` [B, n, 1]).
 """
@@ -144,6 +146,25 @@ class _Batches:
         return self.kind == "markov" and self.arrays is not None and "data" in self.arrays
 
 
+def _holds_trajectories(path: Path) -> bool:
+    with np.load(str(path)) as z:
+        return "data" in z.files
+
+
+def _trajectory_batches(routine, cfg, dev, path: Path, batch_size: Optional[int], mode: str, k: int, **kw):
+    """The training set of a trajectory file on the device (builders/markov_data.py); `f` / `mu` go along when the routine
+    appends them."""
+    from .builders.markov_data import MarkovTrajectoryData
+    with np.load(str(path)) as z:
+        arrays = {name: z[name].astype(np.float32) for name in ("data", "f", "mu") if name in z.files}
+    missing = [name for name, on in (("f", routine.append_force), ("mu", routine.append_mu)) if on and name not in arrays]
+    if missing:
+        raise ValueError(f"{path}: arrays {missing} missing (found {sorted(arrays)})")
+    return MarkovTrajectoryData(arrays["data"], arrays.get("f") if routine.append_force else None,
+                                arrays.get("mu") if routine.append_mu else None, device=dev,
+                                batch_size=batch_size or int(cfg.get("builder", {}).get("batch_size", 19)), mode=mode, k=k, **kw)
+
+
 def _train_step(routine, kind, batch, epoch, step):
     if kind == "rollout":
         return routine.training_step(batch, step)[0]
@@ -210,6 +231,14 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
                                                          "f, mu, corr_data]); valid_loss becomes the trajectory loss of "
                                                          "validation_step over its first batch"),
           batch_size: Optional[int] = None, grid: int = 64, size: Optional[List[int]] = Option(None, help="mesh size"),
+          epochs: int = Option(0, help="trajectory training file: run this many whole epochs instead of --steps"),
+          no_shuffle: bool = Option(False, "--no-shuffle", help="trajectory training file: pairs in (b t) order, not a permutation "
+                                                                "per epoch"),
+          drop_last: bool = Option(False, "--drop-last", help="trajectory training file: drop the short last batch of an epoch"),
+          pair_stride: Optional[int] = Option(None, help="trajectory training file: steps k between a pair's input and target "
+                                                         "(default 1)"),
+          pair_mode: Optional[str] = Option(None, help="trajectory training file: ns_markov (inputs k ... T-1-k, with dx / dy; the "
+                                                       "default) or kolmogorov (inputs 0 ... T-1-k)"),
           device: Optional[str] = Option(None, hidden=True)):
     """Train: build the routine from CONFIG (+ `a.b=c` overrides) and run fused optimisation steps."""
     cfg = load_config(str(config_path), overrides or [])
@@ -220,9 +249,25 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     kind = _kind(routine)
     if kind == "pointcloud" and world > 1:
         raise NotImplementedError("PointCloudExperiment: data parallel training is not built (one process, one GPU)")
-    batches = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial, rank=rank, world=world)
-    if batches.trajectories:
-        raise ValueError(f"{data}: a trajectory file cannot be trained on (training takes x / y pairs); pass it as --valid-data")
+    # a trajectory file is trained on when the command says how: any of the options below selects the pair rule and the epoch
+    # order (each has a default); without one of them the file is refused as before
+    as_trajectories = bool(epochs or no_shuffle or drop_last or pair_stride is not None or pair_mode is not None)
+    if as_trajectories:
+        if kind != "markov" or data is None or not _holds_trajectories(data):
+            raise ValueError("--epochs, --no-shuffle, --drop-last, --pair-stride and --pair-mode need a trajectory training file: "
+                             "the Markov routine with --data FILE holding data [n, M, N, T]")
+        if epochs < 0 or (epochs and steps_per_epoch):
+            raise ValueError("--epochs is a positive number of whole epochs and sets the epoch length itself (no --steps-per-epoch)")
+        batches = _trajectory_batches(routine, cfg, dev, data, batch_size, pair_mode or "ns_markov", 1 if pair_stride is None else pair_stride,
+                                      seed=7231 + trial, shuffle=not no_shuffle, drop_last=drop_last, rank=rank, world=world)
+        if epochs:
+            steps, steps_per_epoch = epochs * len(batches), len(batches)
+    else:
+        batches = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial, rank=rank, world=world)
+        if batches.trajectories:
+            raise ValueError(f"{data}: a trajectory file cannot be trained on as it is (training takes x / y pairs); pass it as "
+                             f"--valid-data, or say how pairs are drawn from it: --pair-mode ns_markov|kolmogorov (or any of "
+                             f"--pair-stride, --epochs, --no-shuffle, --drop-last)")
     valid_batch = None
     if valid_data is not None:
         if kind != "markov":
@@ -248,6 +293,8 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
         for _ in range(accumulation_batches):
             routine.training_step(next(it), epoch=0)
         epoch = max(epoch, 1)
+    if epochs:      # whole epochs from here on: what the statistics pass left of its epoch is not trained on
+        it = iter(batches)
     if hasattr(routine, "current_epoch"):
         routine.current_epoch = epoch
     if dev.type == "cuda":
@@ -277,7 +324,8 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     if dev.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    summary = dict(steps=steps, batch=batches.B, world_size=world, steps_per_s=round(steps / max(dt, 1e-9), 2),
+    summary = dict(steps=steps, batch=batches.B if isinstance(batches, _Batches) else batches.batch_size, world_size=world,
+                   **(dict(epochs=epochs) if epochs else {}), steps_per_s=round(steps / max(dt, 1e-9), 2),
                    resumed_from_step=start["global_step"])
     if out_dir is not None:
         gs = start["global_step"] + steps
@@ -441,12 +489,15 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
                   cycles: int = Option(2, help="--force random: harmonics per direction"),
                   scaling: float = Option(0.1, help="--force random: factor on the summed harmonics"),
                   ssr: int = Option(1, help="keep every ssr-th grid point of the solutions (the builders' stride subsampling)"),
+                  train_trajectories: bool = Option(False, "--train-trajectories",
+                                                    help="write PATH.train.npz as whole trajectories like the other two splits "
+                                                         "(`train --data` draws its pairs from them on the device)"),
                   device: Optional[str] = Option(None, hidden=True)):
     """Generate 2-D Navier-Stokes trajectories (the reference's `fourierflow generate navier-stokes`: GaussianRF initial vorticity,
     the Crank-Nicolson solver, the same options and seeding) and write them as the .npz files `train` / `test` / `predict` read:
-    PATH.train.npz holds x / y pairs [, f, mu], PATH.valid.npz and PATH.test.npz whole trajectories data [n, M, N, T], times
-    [, f, mu].  `f` is written for --force random, `mu` when --mu-min and --mu-max differ.  Each split is solved --batch-size
-    trajectories at a time, with a shorter last batch where that does not divide the split, and written batch by batch."""
+    PATH.train.npz holds x / y pairs [, f, mu] (with --train-trajectories: whole trajectories like the other two), PATH.valid.npz
+    and PATH.test.npz whole trajectories data [n, M, N, T], times [, f, mu].  `f` is written for --force random, `mu` when
+    --mu-min and --mu-max differ.  Each split is solved --batch-size trajectories at a time, with a shorter last batch where that does not divide the split, and written batch by batch."""
     import os
 
     from typer import BadParameter
@@ -469,7 +520,8 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
     for split, n in (("train", n_train), ("valid", n_valid), ("test", n_test)):
         if n <= 0:
             continue
-        rows_per_sample = pairs if split == "train" else 1      # the per-sample f and mu are repeated for every pair
+        as_pairs = split == "train" and not train_trajectories
+        rows_per_sample = pairs if as_pairs else 1      # the per-sample f and mu are repeated for every pair
         sink = _NpzStream(f"{path}.{split}.npz", n * rows_per_sample)
         done = 0
         while done < n:
@@ -482,7 +534,7 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
             sol, f = solve_navier_stokes_2d(w0, nu, t, delta, steps, cycles, scaling, None, force, False)
             sol = sol[:, ::ssr, ::ssr]
             row = done * rows_per_sample
-            if split == "train":
+            if as_pairs:
                 x, y = _training_pairs(sol)
                 sink.put("x", row, x)
                 sink.put("y", row, y)

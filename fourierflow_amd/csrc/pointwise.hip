@@ -668,6 +668,48 @@ __global__ __launch_bounds__(256) void markov_traj_metrics_kernel(const float* _
     }
 }
 
+// ---- Markov training pairs ------------------------------------------------------------------------------------
+// One launch per batch: block (slice, sample) looks up its sample's pair id and walks the pixels of its slice, reading t - k, t
+// and t + k from the pixel's own T-row of the time-last set (4-byte accesses T floats apart, as in the trajectory step above) and
+// writing the pixel-major outputs coalesced.  An id outside [0, total) reads nothing of the set and fills its sample with NaN.
+struct MarkovPairs {
+    const float* data;
+    const int32_t* ids;
+    float *x, *y, *dx, *dy;
+    const float* f;
+    float* f_out;
+    const float* mu;
+    float* mu_out;
+    int n, T, t0, k, P, total;      // n = M N pixels per field; total = trajectories x P
+};
+
+__global__ __launch_bounds__(256) void markov_pairs_kernel(MarkovPairs a) {
+    const int i = blockIdx.y, S = gridDim.x;
+    const int chunk = (a.n + S - 1) / S;
+    const int beg = blockIdx.x * chunk, end = min(a.n, beg + chunk);
+    const int p = a.ids[i];
+    const bool ok = (unsigned)p < (unsigned)a.total;
+    const int b = ok ? p / a.P : 0, t = ok ? a.t0 + p % a.P : 0;
+    const float nan = __builtin_nanf("");
+    const long src = (long)b * a.n, dst = (long)i * a.n;
+    if (a.mu_out && blockIdx.x == 0 && threadIdx.x == 0) a.mu_out[i] = ok ? a.mu[b] : nan;
+    for (int e = beg + threadIdx.x; e < end; e += 256) {
+        float xv = nan, yv = nan, pv = nan, fv = nan;
+        if (ok) {
+            const float* row = a.data + (src + e) * a.T;
+            xv = row[t];
+            if (a.y || a.dy) yv = row[t + a.k];
+            if (a.dx) pv = row[t - a.k];
+            if (a.f_out) fv = a.f[src + e];
+        }
+        if (a.x) a.x[dst + e] = xv;
+        if (a.y) a.y[dst + e] = yv;
+        if (a.dx) a.dx[dst + e] = xv - pv;
+        if (a.dy) a.dy[dst + e] = yv - xv;
+        if (a.f_out) a.f_out[dst + e] = fv;
+    }
+}
+
 // ---- fused flat AdamW ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
@@ -1020,6 +1062,20 @@ extern "C" int ffno_markov_traj_metrics(const float* sums, float* metrics, int B
     if ((long)M * N > 0x7fffffffL) return FFNO_EUNSUPPORTED;
     FFNO_LAUNCH(markov_traj_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, metrics, B, lploss_slices(M * N),
                 n_steps, threshold);
+    return pw_status();
+}
+
+// (one pixel per thread up to 64 slices of a field: a launch of many short, latency-bound row reads wants its workgroups wide)
+extern "C" int ffno_markov_pairs(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f,
+                                 float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k, int P,
+                                 int B, void* stream) {
+    if (!data || !ids || (!x && !y && !dx && !dy) || n <= 0 || M <= 0 || N <= 0 || T <= 0 || k <= 0 || P <= 0 || B <= 0 || t0 < 0)
+        return FFNO_EINVAL;
+    if ((long)t0 + P - 1 + k > (long)T - 1 || (dx && t0 < k) || (f_out && !f) || (mu_out && !mu)) return FFNO_EINVAL;
+    if ((long)M * N > 0x7fffffffL || (long)n * P > 0x7fffffffL || B > 65535) return FFNO_EUNSUPPORTED;
+    const int px = M * N;
+    MarkovPairs a{data, ids, x, y, dx, dy, f, f_out, mu, mu_out, px, T, t0, k, P, n * P};
+    FFNO_LAUNCH(markov_pairs_kernel, dim3(max(1, min(64, (px + 255) / 256)), B), dim3(256), 0, (hipStream_t)stream, a);
     return pw_status();
 }
 

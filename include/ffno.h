@@ -875,6 +875,25 @@ int ffno_markov_traj_metrics(const float* sums, float* metrics, int B, int M, in
                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training batches of the Markov routine drawn from whole trajectories on the device: what indexing the reference's
+ * NavierStokesTrainingDataset (builders/ns_markov.py:62-91) or KolmogorovTorchDataset (builders/kolmogorov.py:111-139) with B
+ * indices and collating the items gives, in one launch, fp32, no atomics, bit-reproducible (every output is a copy or one fp32
+ * subtraction).  data [n][M][N][T] is the time-last set that the files hold and ffno_markov_traj_step reads; ids is a DEVICE
+ * array of B pair ids.  With P pairs per trajectory, id p = ids[i] names trajectory b = p / P and input time t = t0 + p % P:
+ *   x[i][m][n]  = data[b][m][n][t]                 y[i][m][n]  = data[b][m][n][t + k]
+ *   dx[i][m][n] = x - data[b][m][n][t - k]         dy[i][m][n] = y - x
+ *   f_out[i][m][n] = f[b][m][n]  (f [n][M][N])     mu_out[i]   = mu[b]  (mu [n])
+ * Every output is optional (NULL = not written); at least one of x, y, dx, dy is required.  NavierStokesTrainingDataset is
+ * t0 = 1, k = 1, P = T - 2; KolmogorovTorchDataset is t0 = 0, k, P = T - k without dx / dy.
+ * FFNO_EINVAL: NULL data / ids, a non-positive size, t0 + P - 1 + k > T - 1, dx with t0 < k, f_out without f, mu_out without mu.
+ * An id outside [0, n P) cannot be seen from the host: the kernel reads nothing of the set for it and fills every requested
+ * output of that sample with NaN (the call still returns 0).
+ * --------------------------------------------------------------------------------------------- */
+int ffno_markov_pairs(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f,
+                      float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k, int P, int B,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused AdamW over one flat parameter buffer (torch.optim.AdamW semantics, config.yaml:36-40):
  *   p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
  *   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)        with g := grad * grad_scale

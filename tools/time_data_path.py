@@ -1,0 +1,107 @@
+#!/usr/bin/env python3
+"""What the training data path costs per step of the Markov routine (markov/24: 24 layers, width 64, 16 modes; batch 32,
+64 x 64) on the GPU, with the batches coming from
+
+  (a) pairs:         an x / y / dx / dy pair file through the CLI's `_Batches` (a host slice and a synchronous copy per step),
+  (b) trajectories:  the same set as whole trajectories through MarkovTrajectoryData (one ffno_markov_pairs launch per step,
+                     a shuffled permutation per epoch),
+  (c) fixed:         one batch that stays on the device (the floor `bench.py` measures),
+
+as the median of 5 repeats of --steps steps each, the three sides alternating within a repeat; and the time of one
+ffno_markov_pairs launch at that shape (device events around --launches back-to-back launches, so dispatch included).  One JSON
+line; profiles/markov_data_path.md holds a run.  From the repository root:  python tools/time_data_path.py"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from fourierflow_amd.builders.markov_data import MarkovTrajectoryData  # noqa: E402
+from fourierflow_amd.cli import _Batches  # noqa: E402
+from fourierflow_amd.modules import FNOFactorized2DBlock  # noqa: E402
+from fourierflow_amd.routines import Grid2DMarkovExperiment  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=100, help="training steps per repeat")
+ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--launches", type=int, default=1000, help="ffno_markov_pairs launches between the two device events")
+ap.add_argument("--trajectories", type=int, default=64)
+ap.add_argument("--layers", type=int, default=24)
+args = ap.parse_args()
+
+B, G, T = 32, 64, 20
+dev = torch.device("cuda:0")
+KW = dict(modes=16, width=64, n_layers=args.layers, input_dim=3, share_weight=True, factor=4, ff_weight_norm=True, gain=0.1)
+torch.manual_seed(0)
+exp = Grid2DMarkovExperiment(FNOFactorized2DBlock(**KW)).to(dev)
+
+rs = np.random.RandomState(0)
+data = rs.standard_normal((args.trajectories, G, G, T)).astype(np.float32)
+
+
+def expand(a):
+    return np.ascontiguousarray(np.moveaxis(a, -1, 1)).reshape(-1, G, G, 1)
+
+
+with tempfile.TemporaryDirectory() as tmp:
+    path = os.path.join(tmp, "pairs.npz")
+    np.savez(path, x=expand(data[..., 1:-1]), y=expand(data[..., 2:]), dx=expand(data[..., 1:-1] - data[..., :-2]),
+             dy=expand(data[..., 2:] - data[..., 1:-1]))
+    pairs = _Batches(exp, {}, dev, path, B, G, None, seed=0)
+trajectories = MarkovTrajectoryData(data, device=dev, batch_size=B, seed=0)
+fixed = next(iter(MarkovTrajectoryData(data, device=dev, batch_size=B, seed=0)))
+
+
+def forever(batch):
+    while True:
+        yield batch
+
+
+sources = dict(pairs=iter(pairs), trajectories=iter(trajectories), fixed=forever(fixed))
+for _ in range(4):      # epoch 0: the normaliser statistics
+    exp.training_step(next(sources["trajectories"]), epoch=0)
+
+
+def timed(it, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        exp.training_step(next(it), epoch=1)
+    torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / steps
+
+
+for it in sources.values():
+    timed(it, 10)
+rounds = {name: [] for name in sources}
+for _ in range(args.repeats):
+    for name, it in sources.items():
+        rounds[name].append(timed(it, args.steps))
+
+ids = torch.randperm(trajectories.n_pairs, generator=torch.Generator().manual_seed(1)).to(torch.int32).to(dev)
+for _ in range(10):
+    trajectories.gather(ids, 0, B)
+launch_us = []
+for _ in range(args.repeats):
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for j in range(args.launches):
+        trajectories.gather(ids, (j * B) % (trajectories.n_pairs - B + 1), B)
+    stop.record()
+    torch.cuda.synchronize()
+    launch_us.append(1e3 * start.elapsed_time(stop) / args.launches)
+
+out = dict(shape=dict(batch=B, grid=G, T=T, trajectories=args.trajectories, layers=args.layers, steps=args.steps))
+for name, r in rounds.items():
+    out[name] = dict(ms_per_step=round(statistics.median(r), 4), spread_ms=round(max(r) - min(r), 4), repeats=[round(v, 4) for v in r])
+out["trajectories_minus_pairs_ms"] = round(out["trajectories"]["ms_per_step"] - out["pairs"]["ms_per_step"], 4)
+out["markov_pairs_launch_us"] = dict(median=round(statistics.median(launch_us), 3), repeats=[round(v, 3) for v in launch_us])
+print(json.dumps(out))
