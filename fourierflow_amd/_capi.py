@@ -138,6 +138,15 @@ class PcHeadParams(C.Structure):
     _fields_ = [(n, P) for n in ("bs_w", "bs_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
 
 
+class GatherField(C.Structure):
+    """Mirror of ``ffno_gather_field`` (include/ffno.h)."""
+    _fields_ = [("src", P), ("dst", P), ("src_sample", C.c_int64), ("src_offset", C.c_int64), ("src_q", C.c_int64),
+                ("src_r", C.c_int64), ("dst_sample", C.c_int64), ("dst_offset", C.c_int64), ("dst_q", C.c_int64),
+                ("dst_r", C.c_int64), ("Q", C.c_int32), ("R", C.c_int32)]
+
+
+GATHER_MAX_FIELDS = 8      # FFNO_GATHER_MAX_FIELDS
+
 SIGNATURES = {
     "ffno_build_target": (C.c_char_p, []),
     "ffno_abi_version": (I, []),
@@ -265,6 +274,7 @@ SIGNATURES = {
     "ffno_markov_traj_step": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "ffno_markov_traj_metrics": (I, [P, P, I, I, I, I, F, P]),
     "ffno_markov_pairs": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "ffno_sample_gather": (I, [P, I, P, I, I, P]),
     "ffno_adamw_flat":(I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_adam_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_axpy": (I, [P, P, F, SZ, P]),

@@ -1,6 +1,9 @@
-"""Data builders.  Of the reference's ``fourierflow.builders`` the synthetic Navier-Stokes generator and the training set of the
-Markov routine are built (``MarkovTrajectoryData``: the pair datasets of ns_markov.py / kolmogorov.py drawn on the device from
-whole trajectories); the other dataset classes slice files, and the training commands read ``.npz`` files directly
-(fourierflow_amd/cli.py)."""
+"""Data builders.  Of the reference's ``fourierflow.builders`` these are built: the synthetic Navier-Stokes generator; the
+training set of the Markov routine (``MarkovTrajectoryData``: the pair datasets of ns_markov.py / kolmogorov.py drawn on the
+device from whole trajectories); and the dataset builders of the mesh and point-cloud experiments (``StructuredMesh2DBuilder``,
+``PlasticityBuilder``, ``ElasticityBuilder``: the datasets' own files, split as the reference splits them, held on the device as
+``DeviceSampleData``).  Without a builder the training commands read ``.npz`` files directly (fourierflow_amd/cli.py)."""
 from .markov_data import MarkovTrajectoryData  # noqa: F401
+from .mesh_data import ElasticityBuilder, PlasticityBuilder, StructuredMesh2DBuilder  # noqa: F401
+from .sample_data import DeviceSampleData  # noqa: F401
 from .synthetic import Force, GaussianRF, random_force, solve_navier_stokes_2d  # noqa: F401

@@ -9,7 +9,7 @@ commands/predict.py:24-110) for the routines built here, with the same positiona
 
 What is NOT here is the reference's control plane: Hydra (the loader of fourierflow_amd/config.py resolves the same
 interpolations), Lightning (the routines run their own fused step), wandb (one JSON line per logged step on stdout)
-and the dataset builders.  Batches therefore come from ``--data FILE.npz`` (arrays named like
+and most dataset builders.  Without ``--builder``, batches come from ``--data FILE.npz`` (arrays named like
 the builder's batches: ``x``/``y`` [, ``f``, ``mu``] for the Markov and mesh routines, ``data`` for the rollout routine;
 for the Markov routine a file with ``data`` [n, M, N, T] [, ``times``, ``f``, ``mu``, ``corr_data``] is a TRAJECTORY file, what
 its validation / test loaders deliver: `test --data` and `train --valid-data` run the autoregressive metrics on it, and
@@ -17,6 +17,11 @@ its validation / test loaders deliver: `test --data` and `train --valid-data` ru
 on the device (builders/markov_data.py; without one of these options a trajectory training file is refused);
 ``xy``/``rr``/``sigma`` for the point-cloud routine; first axis = samples) or, without it, are synthetic N(0,1) fields of the
 configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless ``--size``, ``rr`` [B, 42], ``sigma`` [B, n, 1]).
+
+``train CONFIG --builder`` and ``test CONFIG --builder`` run the mesh and point-cloud routines the way the reference does: on the
+dataset files of the config's ``builder`` section (StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder:
+builders/mesh_data.py), split by ``train_size`` / ``valid_size`` / ``test_size``, in shuffled epochs drawn on the device, with the
+validation split evaluated after every epoch and the best checkpoint kept.
 """
 from __future__ import annotations
 
@@ -165,6 +170,111 @@ def _trajectory_batches(routine, cfg, dev, path: Path, batch_size: Optional[int]
                                 batch_size=batch_size or int(cfg.get("builder", {}).get("batch_size", 19)), mode=mode, k=k, **kw)
 
 
+BUILDERS = ("StructuredMesh2DBuilder", "PlasticityBuilder", "ElasticityBuilder")
+
+
+def _instantiate_builder(cfg, kind: str, batch_size: Optional[int]):
+    """The config's `builder` section as one of builders/mesh_data.py (`${oc.env:DATA_ROOT}` resolved like everywhere else)."""
+    from .config import instantiate
+    node = dict(cfg.get("builder") or {})
+    name = str(node.get("_target_", "")).rpartition(".")[2]
+    routines = {"StructuredMesh2DBuilder": "mesh", "PlasticityBuilder": "mesh", "ElasticityBuilder": "pointcloud"}
+    if routines.get(name) != kind:
+        raise ValueError(f"--builder runs StructuredMeshExperiment on {BUILDERS[0]} / {BUILDERS[1]} and PointCloudExperiment on "
+                         f"{BUILDERS[2]}; this config pairs a {kind} routine with builder {name or '(none)'!r}")
+    if batch_size:
+        node["batch_size"] = batch_size
+    return instantiate(node)
+
+
+def _split_loss(routine, data) -> float:
+    """The sample-weighted mean of `validation_step` over every batch of `data`, short last batch included (what Lightning logs
+    for the epoch), under eval(): accumulated on the device, read once."""
+    was_training = routine.training
+    routine.eval()
+    try:
+        with torch.no_grad():
+            total, n = None, 0
+            for batch in data.epoch():
+                B = len(next(iter(batch.values())))
+                part = routine.validation_step(batch).reshape(()).double() * B
+                total = part if total is None else total + part
+                n += B
+            return float(total.item()) / n
+    finally:
+        routine.train(was_training)
+
+
+def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial, checkpoint_id, no_logging, force, resume, epochs,
+                        no_shuffle, drop_last, batch_size):
+    """`train --builder`: whole epochs over the builder's training split, validation over its whole validation split after every
+    epoch, the best checkpoint kept (CustomModelCheckpoint: monitor valid_loss, mode min, top 1), last.ckpt every epoch."""
+    bld = _instantiate_builder(cfg, kind, batch_size)
+    n_epochs = epochs or int((cfg.get("trainer") or {}).get("max_epochs", 0))
+    if n_epochs < 1:
+        raise ValueError("--builder runs whole epochs: pass --epochs E or set trainer.max_epochs in the config")
+    train_set = bld.train_data(dev, seed=7231 + trial, rank=rank, world=world, shuffle=not no_shuffle, drop_last=drop_last)
+    valid_set = bld.valid_data(dev)      # every rank validates the whole split
+    trial_dir = None if no_logging else _trial_dir(config_path.parent, trial, checkpoint_id, create=rank == 0)
+    out_dir = trial_dir if rank == 0 else None
+    if out_dir is not None and force and not resume:
+        for old in out_dir.glob("*.ckpt"):
+            old.unlink()
+    start, best = dict(epoch=0, global_step=0), math.inf
+    if resume:
+        if trial_dir is None or not (trial_dir / "last.ckpt").exists():
+            raise FileNotFoundError("--resume needs checkpoints/trial-<trial>-*/last.ckpt (commands/train.py:74-80)")
+        start = routine.resume_from_checkpoint(str(trial_dir / "last.ckpt"))
+        # the best validation loss so far: last.ckpt carries it, as Lightning's carries its checkpoint callback's state
+        saved = torch.load(str(trial_dir / "last.ckpt"), map_location="cpu", weights_only=False).get("callbacks") or {}
+        best = float((saved.get("ModelCheckpoint") or {}).get("best_model_score", math.inf))
+        for _ in range(start["epoch"] if train_set.shuffle else 0):      # the permutations of the epochs already run
+            train_set._epoch_ids()
+    if hasattr(routine, "current_epoch"):
+        routine.current_epoch = start["epoch"]
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    gs = start["global_step"]
+    for epoch in range(start["epoch"], n_epochs):
+        loss = None
+        for batch in train_set.epoch():
+            loss = routine.training_step(batch, gs)
+            gs += 1
+        lv, lr = float(loss.item()), routine.trainer().current_lr()
+        if not math.isfinite(lv):
+            raise FloatingPointError(f"non-finite training loss at the end of epoch {epoch} (step {gs - 1}): check the data and the "
+                                     f"learning rate")
+        if hasattr(routine, "on_train_epoch_end"):
+            routine.on_train_epoch_end()
+        vl = _split_loss(routine, valid_set)
+        improved = vl < best
+        if out_dir is not None:
+            if improved:
+                for old in out_dir.glob("epoch*.ckpt"):
+                    old.unlink()
+                routine.save_checkpoint(str(out_dir / f"epoch={epoch + 1}-step={gs}-valid_loss={vl:.5f}.ckpt"), epoch=epoch + 1,
+                                        global_step=gs)
+        best = min(best, vl)
+        if out_dir is not None:
+            last = routine.checkpoint_dict(epoch + 1, gs)
+            last["callbacks"] = {"ModelCheckpoint": dict(monitor="valid_loss", best_model_score=best)}
+            torch.save(last, str(out_dir / "last.ckpt"))
+        if rank == 0:
+            print(json.dumps(dict(epoch=epoch + 1, step=gs, train_loss=round(lv, 6), lr=lr, valid_loss=round(vl, 6),
+                                  best=improved)), flush=True)
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    steps = gs - start["global_step"]
+    if rank == 0:
+        print(json.dumps(dict(steps=steps, batch=train_set.batch_size, world_size=world, epochs=n_epochs - start["epoch"],
+                              steps_per_s=round(steps / max(dt, 1e-9), 2), resumed_from_step=start["global_step"],
+                              **({} if best == math.inf else dict(valid_loss=round(best, 6))))), flush=True)
+    if world > 1:
+        torch.distributed.barrier()
+
+
 def _train_step(routine, kind, batch, epoch, step):
     if kind == "rollout":
         return routine.training_step(batch, step)[0]
@@ -239,6 +349,10 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
                                                          "(default 1)"),
           pair_mode: Optional[str] = Option(None, help="trajectory training file: ns_markov (inputs k ... T-1-k, with dx / dy; the "
                                                        "default) or kolmogorov (inputs 0 ... T-1-k)"),
+          builder: bool = Option(False, "--builder", help="mesh and point-cloud routines: train on the dataset files of the config's "
+                                                          "`builder` section (StructuredMesh2DBuilder, PlasticityBuilder, "
+                                                          "ElasticityBuilder) for --epochs (default trainer.max_epochs) whole "
+                                                          "epochs, validating on the held-out split after each"),
           device: Optional[str] = Option(None, hidden=True)):
     """Train: build the routine from CONFIG (+ `a.b=c` overrides) and run fused optimisation steps."""
     cfg = load_config(str(config_path), overrides or [])
@@ -249,6 +363,14 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     kind = _kind(routine)
     if kind == "pointcloud" and world > 1:
         raise NotImplementedError("PointCloudExperiment: data parallel training is not built (one process, one GPU)")
+    if builder:
+        if data is not None or steps_per_epoch:
+            raise ValueError("--builder takes its batches from the config's builder section and runs whole epochs: it goes with "
+                             "neither --data nor --steps-per-epoch")
+        if epochs < 0:
+            raise ValueError("--epochs is a positive number of whole epochs")
+        return _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial, checkpoint_id, no_logging, force, resume,
+                                   epochs, no_shuffle, drop_last, batch_size)
     # a trajectory file is trained on when the command says how: any of the options below selects the pair rule and the epoch
     # order (each has a default); without one of them the file is refused as before
     as_trajectories = bool(epochs or no_shuffle or drop_last or pair_stride is not None or pair_mode is not None)
@@ -347,8 +469,12 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
          map_location: Optional[str] = None, debug: bool = False, no_logging: bool = False,
          batches: int = Option(1, help="test batches to average over"), data: Optional[Path] = None,
          batch_size: Optional[int] = None, grid: int = 64, size: Optional[List[int]] = None,
+         builder: bool = Option(False, "--builder", help="mesh and point-cloud routines: the loss over the whole test split of the "
+                                                         "config's `builder` section"),
          device: Optional[str] = Option(None, hidden=True)):
     """Test: load the best checkpoint of the trial (or `checkpoint_path=...` override) and report the test metrics."""
+    if builder and data is not None:
+        raise ValueError("--builder takes the test split from the config's builder section: it does not go with --data")
     cfg = load_config(str(config_path), overrides or [])
     dev = _device(device)
     routine = build_routine(cfg).to(dev)
@@ -357,6 +483,11 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
     routine.load_lightning_model_state(str(ckpt), map_location)
     routine.to(dev)
     routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
+    if builder:
+        test_set = _instantiate_builder(cfg, kind, batch_size).test_data(dev)
+        print(json.dumps(dict(checkpoint=str(ckpt), test_loss=round(_split_loss(routine, test_set), 6), samples=test_set.n)),
+              flush=True)
+        return
     src = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial)
     it = iter(src)
     acc: Dict[str, float] = {}

@@ -5,8 +5,10 @@ The reference composes ``experiments/**/config.yaml`` with Hydra, resolves the c
 ``_target_`` nodes (commands/train.py:38-67).  This module does the same for the part of a config that
 drives the hot path -- ``routine`` with its ``conv`` / ``model``, ``optimizer`` and ``scheduler`` nodes -- and
 maps ``fourierflow.*`` targets onto their MI355X-native mirrors, so an unmodified torus_li config builds
-the HIP-backed routine.  ``builder`` / ``trainer`` / ``callbacks`` / ``wandb`` sections are parsed but not
-instantiated (data loading and the Lightning control plane are out of scope).
+the HIP-backed routine.  ``build_routine`` leaves the other sections alone; of them the CLI's ``--builder`` instantiates a
+``builder`` section that names StructuredMesh2DBuilder, PlasticityBuilder or ElasticityBuilder (builders/mesh_data.py) and
+reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
+scope).
 """
 from __future__ import annotations
 
@@ -36,6 +38,9 @@ TARGET_MAP = {
     "fourierflow.routines.Grid2DRolloutExperiment": "fourierflow_amd.routines.Grid2DRolloutExperiment",
     "fourierflow.routines.StructuredMeshExperiment": "fourierflow_amd.routines.StructuredMeshExperiment",
     "fourierflow.routines.PointCloudExperiment": "fourierflow_amd.routines.PointCloudExperiment",
+    "fourierflow.builders.StructuredMesh2DBuilder": "fourierflow_amd.builders.StructuredMesh2DBuilder",
+    "fourierflow.builders.PlasticityBuilder": "fourierflow_amd.builders.PlasticityBuilder",
+    "fourierflow.builders.ElasticityBuilder": "fourierflow_amd.builders.ElasticityBuilder",
 }
 _INTERP = re.compile(r"^\$\{\s*([\w.]+)\s*:\s*(.*?)\s*\}$")
 

@@ -710,6 +710,51 @@ __global__ __launch_bounds__(256) void markov_pairs_kernel(MarkovPairs a) {
     }
 }
 
+// ---- sample gather ------------------------------------------------------------------------------------------
+// One launch per batch for every field of it: block (slice, sample, field) looks up its sample's id and copies its slice of the
+// field's Q x R values between two strided layouts.  A unit of work is one value, or -- where the host found the inner run
+// contiguous on both sides with rows a multiple of 16 bytes apart (`vec`) and this sample's two base addresses are 16-byte
+// aligned -- four values of a row through one 16-byte access, the row's last R % 4 values one by one.  Consecutive lanes take
+// consecutive units, so the contiguous side of every copy is coalesced.  An id outside [0, n) reads and writes nothing.
+struct GatherField {
+    const float* src;
+    float* dst;
+    long src_sample, src_offset, src_q, src_r, dst_sample, dst_offset, dst_q, dst_r;
+    int Q, R, vec;
+};
+struct SampleGather {
+    GatherField f[FFNO_GATHER_MAX_FIELDS];
+    const int32_t* ids;
+    int n;
+};
+
+__global__ __launch_bounds__(256) void sample_gather_kernel(SampleGather a) {
+    const GatherField& g = a.f[blockIdx.z];
+    const int i = blockIdx.y, S = gridDim.x;
+    const int id = a.ids[i];
+    if ((unsigned)id >= (unsigned)a.n) return;
+    const float* sp = g.src + (long)id * g.src_sample + g.src_offset;
+    float* dp = g.dst + (long)i * g.dst_sample + g.dst_offset;
+    const bool wide = g.vec && (((uintptr_t)sp | (uintptr_t)dp) & 15) == 0;
+    const int W = wide ? 4 : 1;
+    const int U = (g.R + W - 1) / W;                     // units per row
+    const long units = (long)g.Q * U;
+    const long chunk = (units + S - 1) / S;
+    const long beg = blockIdx.x * chunk, end = beg + chunk < units ? beg + chunk : units;
+    for (long u = beg + threadIdx.x; u < end; u += 256) {
+        const long q = u / U;
+        const int r = (int)(u - q * U) * W;
+        const float* s = sp + q * g.src_q + r * g.src_r;
+        float* d = dp + q * g.dst_q + r * g.dst_r;
+        if (wide && r + 4 <= g.R) {
+            *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(s);
+        } else {
+            const int m = min(W, g.R - r);               // (wide: the row's tail; both strides are 1 there)
+            for (int j = 0; j < m; ++j) d[j * g.dst_r] = s[j * g.src_r];
+        }
+    }
+}
+
 // ---- fused flat AdamW ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
@@ -1076,6 +1121,35 @@ extern "C" int ffno_markov_pairs(const float* data, const int32_t* ids, float* x
     const int px = M * N;
     MarkovPairs a{data, ids, x, y, dx, dy, f, f_out, mu, mu_out, px, T, t0, k, P, n * P};
     FFNO_LAUNCH(markov_pairs_kernel, dim3(max(1, min(64, (px + 255) / 256)), B), dim3(256), 0, (hipStream_t)stream, a);
+    return pw_status();
+}
+
+// (up to 64 slices of 256 lanes per sample and field, sized by the launch's largest field; a slice of a smaller field that
+// starts past its end returns at once)
+extern "C" int ffno_sample_gather(const ffno_gather_field* fields, int n_fields, const int32_t* ids, int n, int B, void* stream) {
+    if (!fields || !ids || n_fields <= 0 || n_fields > FFNO_GATHER_MAX_FIELDS || n <= 0 || B <= 0) return FFNO_EINVAL;
+    SampleGather a{};
+    long most = 1;
+    for (int k = 0; k < n_fields; ++k) {
+        const ffno_gather_field& f = fields[k];
+        if (!f.src || !f.dst || f.Q <= 0 || f.R <= 0) return FFNO_EINVAL;
+        if (f.src_sample < 0 || f.src_offset < 0 || f.src_q < 0 || f.src_r < 0 || f.dst_sample < 0 || f.dst_offset < 0 ||
+            f.dst_q < 0 || f.dst_r < 0)
+            return FFNO_EINVAL;
+        if ((long)f.Q * f.R > 0x7fffffffL) return FFNO_EUNSUPPORTED;
+        GatherField& g = a.f[k];
+        g = GatherField{f.src, f.dst, f.src_sample, f.src_offset, f.src_q, f.src_r, f.dst_sample, f.dst_offset, f.dst_q, f.dst_r,
+                        f.Q, f.R, 0};
+        if (g.src_r == 1 && g.dst_r == 1 && g.src_q == g.R && g.dst_q == g.R) g.R *= g.Q, g.Q = 1;      // rows back to back: one run
+        g.vec = g.src_r == 1 && g.dst_r == 1 && g.R >= 4 && (g.Q == 1 || (g.src_q % 4 == 0 && g.dst_q % 4 == 0));
+        const long units = g.vec ? (long)g.Q * ((g.R + 3) / 4) : (long)g.Q * g.R;
+        if (units > most) most = units;
+    }
+    if (B > 65535) return FFNO_EUNSUPPORTED;
+    a.ids = ids;
+    a.n = n;
+    FFNO_LAUNCH(sample_gather_kernel, dim3((unsigned)((most + 255) / 256 < 64 ? (most + 255) / 256 : 64), B, n_fields), dim3(256), 0,
+                (hipStream_t)stream, a);
     return pw_status();
 }
 

@@ -894,6 +894,39 @@ int ffno_markov_pairs(const float* data, const int32_t* ids, float* x, float* y,
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * A training / validation batch drawn from sample sets on the device, every field of it in one launch: what indexing the
+ * reference's map-style datasets (builders/structured_mesh_2d.py:73-85, plasticity.py:68-80, elasticity.py:76-90) with B indices
+ * and collating the items gives, including the layout change those builders make on the host (stack, channel pick, repeat,
+ * permute) -- it happens in the copy.  Copies only: fp32, no arithmetic, no atomics, bitwise.
+ * `fields` is a HOST array of n_fields <= FFNO_GATHER_MAX_FIELDS descriptors (copied into the launch's arguments; nothing is
+ * uploaded); ids is a DEVICE array of B sample ids, so a batch is `ids + offset` of an epoch's permutation.  For field f and
+ * b < B, q < Q, r < R:
+ *   dst[b dst_sample + dst_offset + q dst_q + r dst_r] = src[ids[b] src_sample + src_offset + q src_q + r src_r]
+ * Strides and offsets count floats and are >= 0; a source stride of 0 broadcasts.  Examples (n samples in the set):
+ *   plain rows of L floats         Q = 1, R = L, src_sample = dst_sample = L, src_r = dst_r = 1
+ *   x1, x2 [n][X][Y] -> [B][X][Y][2]  two fields, Q = X Y, R = 1, src_q = 1, dst_q = 2, dst_sample = 2 X Y, dst_offset = 0 / 1
+ *   channel c of [n][C][X][Y]      src_sample = C X Y, src_offset = c X Y
+ *   [n][s1] -> [B][s1][s2 t][1]     Q = s1, R = s2 t, src_q = 1, src_r = 0, dst_q = s2 t, dst_r = 1
+ *   sample axis last, [N][2][n] -> [B][N][2]   src_sample = 1, Q = N, R = 2, src_q = 2 n, src_r = n, dst_q = 2, dst_r = 1
+ * Where a field's inner run is contiguous on both sides (src_r = dst_r = 1; rows a multiple of 4 floats apart, or back to back)
+ * and both addresses of a sample are 16-byte aligned, that sample is copied with 16-byte accesses, else with 4-byte ones.
+ * The extents of src and dst are the caller's: the entry cannot check them.
+ * FFNO_EINVAL: NULL fields / ids / src / dst, n_fields outside 1 ... 8, n, B, Q or R <= 0, a negative stride or offset.
+ * FFNO_EUNSUPPORTED: B > 65535, Q R > 2^31 - 1.
+ * An id outside [0, n) cannot be seen from the host: the kernel reads nothing for it and leaves that sample's destination as
+ * it was (the call still returns 0).
+ * --------------------------------------------------------------------------------------------- */
+#define FFNO_GATHER_MAX_FIELDS 8
+typedef struct ffno_gather_field {
+    const float* src;
+    float* dst;
+    int64_t src_sample, src_offset, src_q, src_r;
+    int64_t dst_sample, dst_offset, dst_q, dst_r;
+    int32_t Q, R;
+} ffno_gather_field;
+int ffno_sample_gather(const ffno_gather_field* fields, int n_fields, const int32_t* ids, int n, int B, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused AdamW over one flat parameter buffer (torch.optim.AdamW semantics, config.yaml:36-40):
  *   p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
  *   p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps)        with g := grad * grad_scale
