@@ -2,8 +2,9 @@
 training set of the Markov routine (``MarkovTrajectoryData``: the pair datasets of ns_markov.py / kolmogorov.py drawn on the
 device from whole trajectories); and the dataset builders of the mesh and point-cloud experiments (``StructuredMesh2DBuilder``,
 ``PlasticityBuilder``, ``ElasticityBuilder``: the datasets' own files, split as the reference splits them, held on the device as
-``DeviceSampleData``).  Without a builder the training commands read ``.npz`` files directly (fourierflow_amd/cli.py)."""
+``DeviceSampleData``) and of the torus_li experiments (``NSMarkovBuilder``, ``NSZongyiBuilder``: builders/ns_data.py).  Without a builder the training commands read ``.npz`` files directly (fourierflow_amd/cli.py)."""
 from .markov_data import MarkovTrajectoryData  # noqa: F401
 from .mesh_data import ElasticityBuilder, PlasticityBuilder, StructuredMesh2DBuilder  # noqa: F401
+from .ns_data import NSMarkovBuilder, NSZongyiBuilder  # noqa: F401
 from .sample_data import DeviceSampleData  # noqa: F401
 from .synthetic import Force, GaussianRF, random_force, solve_navier_stokes_2d  # noqa: F401

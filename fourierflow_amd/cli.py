@@ -18,10 +18,12 @@ on the device (builders/markov_data.py; without one of these options a trajector
 ``xy``/``rr``/``sigma`` for the point-cloud routine; first axis = samples) or, without it, are synthetic N(0,1) fields of the
 configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless ``--size``, ``rr`` [B, 42], ``sigma`` [B, n, 1]).
 
-``train CONFIG --builder`` and ``test CONFIG --builder`` run the mesh and point-cloud routines the way the reference does: on the
-dataset files of the config's ``builder`` section (StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder:
-builders/mesh_data.py), split by ``train_size`` / ``valid_size`` / ``test_size``, in shuffled epochs drawn on the device, with the
-validation split evaluated after every epoch and the best checkpoint kept.
+``train CONFIG --builder`` and ``test CONFIG --builder`` run the routines the way the reference does: on the dataset files of the
+config's ``builder`` section (StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder: builders/mesh_data.py; NSMarkovBuilder,
+NSZongyiBuilder: builders/ns_data.py), split by ``train_size`` / ``valid_size`` / ``test_size``, in shuffled epochs drawn on the
+device, with the validation split evaluated after every epoch and the best checkpoint kept.  For the Markov routine epoch 0 is
+the reference's statistics epoch: one whole pass that only accumulates the normaliser.  ``predict CONFIG --builder`` runs on the
+builder's ``inference_data()`` and reports the reference's ``inference_time``.
 """
 from __future__ import annotations
 
@@ -170,46 +172,77 @@ def _trajectory_batches(routine, cfg, dev, path: Path, batch_size: Optional[int]
                                 batch_size=batch_size or int(cfg.get("builder", {}).get("batch_size", 19)), mode=mode, k=k, **kw)
 
 
-BUILDERS = ("StructuredMesh2DBuilder", "PlasticityBuilder", "ElasticityBuilder")
+# the classes `--builder` runs and the routine each one feeds
+BUILDERS = {"StructuredMesh2DBuilder": "mesh", "PlasticityBuilder": "mesh", "ElasticityBuilder": "pointcloud",
+            "NSMarkovBuilder": "markov", "NSZongyiBuilder": "rollout"}
+_ROUTINES = {"mesh": "StructuredMeshExperiment", "pointcloud": "PointCloudExperiment", "markov": "Grid2DMarkovExperiment",
+             "rollout": "Grid2DRolloutExperiment"}
 
 
-def _instantiate_builder(cfg, kind: str, batch_size: Optional[int]):
-    """The config's `builder` section as one of builders/mesh_data.py (`${oc.env:DATA_ROOT}` resolved like everywhere else)."""
-    from .config import instantiate
+def _instantiate_builder(cfg, kind: str, batch_size: Optional[int], routine=None):
+    """The config's `builder` section as one of builders/mesh_data.py / ns_data.py (`${oc.env:DATA_ROOT}` resolved like everywhere
+    else).  A section that names another builder than the routine's, none at all, or lacks an argument its class requires is
+    refused before anything is read."""
+    import inspect
+
+    from .config import TARGET_MAP, import_string, instantiate
     node = dict(cfg.get("builder") or {})
-    name = str(node.get("_target_", "")).rpartition(".")[2]
-    routines = {"StructuredMesh2DBuilder": "mesh", "PlasticityBuilder": "mesh", "ElasticityBuilder": "pointcloud"}
-    if routines.get(name) != kind:
-        raise ValueError(f"--builder runs StructuredMeshExperiment on {BUILDERS[0]} / {BUILDERS[1]} and PointCloudExperiment on "
-                         f"{BUILDERS[2]}; this config pairs a {kind} routine with builder {name or '(none)'!r}")
+    target = str(node.get("_target_", ""))
+    name = target.rpartition(".")[2]
+    runs = "; ".join(f"{_ROUTINES[k]} on {' / '.join(b for b, kk in BUILDERS.items() if kk == k)}" for k in _ROUTINES)
+    if BUILDERS.get(name) != kind:
+        raise ValueError(f"--builder runs {runs}; this config pairs a {kind} routine with builder {name or '(none)'!r}")
+    cls = import_string(TARGET_MAP.get(target, target))
+    missing = [p.name for p in inspect.signature(cls.__init__).parameters.values()
+               if p.name != "self" and p.default is p.empty and p.kind is p.POSITIONAL_OR_KEYWORD and p.name not in node]
+    if missing:
+        raise ValueError(f"the builder section of this config lacks {', '.join(missing)}, which {name} requires (--builder runs "
+                         f"{runs})")
     if batch_size:
         node["batch_size"] = batch_size
-    return instantiate(node)
+    bld = instantiate(node)
+    if kind == "rollout" and routine is not None and \
+            (bld.n_steps != routine.n_steps or bld.append_pos != bool(routine.append_pos)):
+        raise ValueError(f"builder n_steps = {bld.n_steps}, append_pos = {bld.append_pos} but the routine rolls out n_steps = "
+                         f"{routine.n_steps} with append_pos = {bool(routine.append_pos)}: the batches would not fit")
+    return bld
 
 
-def _split_loss(routine, data) -> float:
-    """The sample-weighted mean of `validation_step` over every batch of `data`, short last batch included (what Lightning logs
-    for the epoch), under eval(): accumulated on the device, read once."""
+def _split_loss(routine, data, step: str = "validation_step", keys=None) -> Dict[str, float]:
+    """The sample-weighted mean, over every batch of `data` (short last batch included), of every key that `step` logs -- what
+    Lightning logs for the epoch -- under eval().  A routine whose step returns the loss alone gives {'valid_loss': ...}.  Tensor
+    values are accumulated on the device and read once at the end; `keys` picks from a step that returns more (per-step tables)."""
     was_training = routine.training
     routine.eval()
     try:
         with torch.no_grad():
-            total, n = None, 0
+            totals, n = {}, 0
             for batch in data.epoch():
                 B = len(next(iter(batch.values())))
-                part = routine.validation_step(batch).reshape(()).double() * B
-                total = part if total is None else total + part
+                out = getattr(routine, step)(batch)
+                if not isinstance(out, dict):
+                    out = {"valid_loss": out}
+                for k in (keys or out):
+                    v = out[k]
+                    part = (v.reshape(()).double() if torch.is_tensor(v) else float(v)) * B
+                    totals[k] = part if k not in totals else totals[k] + part
                 n += B
-            return float(total.item()) / n
+            return {k: float(v) / n for k, v in totals.items()}
     finally:
         routine.train(was_training)
+
+
+TEST_KEYS = {"markov": ("test_loss", "test_loss_avg", "test_time_until", "test_corr"),
+             "rollout": ("test_loss", "test_loss_avg", "test_time_until")}
 
 
 def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial, checkpoint_id, no_logging, force, resume, epochs,
                         no_shuffle, drop_last, batch_size):
     """`train --builder`: whole epochs over the builder's training split, validation over its whole validation split after every
-    epoch, the best checkpoint kept (CustomModelCheckpoint: monitor valid_loss, mode min, top 1), last.ckpt every epoch."""
-    bld = _instantiate_builder(cfg, kind, batch_size)
+    epoch, the best checkpoint kept (CustomModelCheckpoint: monitor valid_loss, mode min, top 1), last.ckpt every epoch.  The
+    Markov routine with `should_normalize` spends epoch 0 on the normaliser statistics alone (grid_2d_markov.py:374-390): no
+    optimisation step is taken, `global_step` stands still, and the epoch is validated and checkpointed like any other."""
+    bld = _instantiate_builder(cfg, kind, batch_size, routine)
     n_epochs = epochs or int((cfg.get("trainer") or {}).get("max_epochs", 0))
     if n_epochs < 1:
         raise ValueError("--builder runs whole epochs: pass --epochs E or set trainer.max_epochs in the config")
@@ -239,15 +272,21 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
     for epoch in range(start["epoch"], n_epochs):
         loss = None
         for batch in train_set.epoch():
-            loss = routine.training_step(batch, gs)
-            gs += 1
-        lv, lr = float(loss.item()), routine.trainer().current_lr()
-        if not math.isfinite(lv):
+            if kind == "markov":
+                loss = routine.training_step(batch, epoch=epoch)      # None in the statistics epoch
+            elif kind == "rollout":
+                loss = routine.training_step(batch, gs)[0]
+            else:
+                loss = routine.training_step(batch, gs)
+            gs += loss is not None
+        lv, lr = None if loss is None else float(loss.item()), routine.trainer().current_lr()
+        if lv is not None and not math.isfinite(lv):
             raise FloatingPointError(f"non-finite training loss at the end of epoch {epoch} (step {gs - 1}): check the data and the "
                                      f"learning rate")
         if hasattr(routine, "on_train_epoch_end"):
             routine.on_train_epoch_end()
-        vl = _split_loss(routine, valid_set)
+        valid = _split_loss(routine, valid_set)
+        vl = valid.pop("valid_loss")
         improved = vl < best
         if out_dir is not None:
             if improved:
@@ -261,8 +300,9 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
             last["callbacks"] = {"ModelCheckpoint": dict(monitor="valid_loss", best_model_score=best)}
             torch.save(last, str(out_dir / "last.ckpt"))
         if rank == 0:
-            print(json.dumps(dict(epoch=epoch + 1, step=gs, train_loss=round(lv, 6), lr=lr, valid_loss=round(vl, 6),
-                                  best=improved)), flush=True)
+            print(json.dumps(dict(epoch=epoch + 1, step=gs, train_loss=None if lv is None else round(lv, 6), lr=lr,
+                                  valid_loss=round(vl, 6), best=improved, **{k: round(v, 6) for k, v in valid.items()})),
+                  flush=True)
     if dev.type == "cuda":
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -349,10 +389,11 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
                                                          "(default 1)"),
           pair_mode: Optional[str] = Option(None, help="trajectory training file: ns_markov (inputs k ... T-1-k, with dx / dy; the "
                                                        "default) or kolmogorov (inputs 0 ... T-1-k)"),
-          builder: bool = Option(False, "--builder", help="mesh and point-cloud routines: train on the dataset files of the config's "
-                                                          "`builder` section (StructuredMesh2DBuilder, PlasticityBuilder, "
-                                                          "ElasticityBuilder) for --epochs (default trainer.max_epochs) whole "
-                                                          "epochs, validating on the held-out split after each"),
+          builder: bool = Option(False, "--builder", help="train on the dataset files of the config's `builder` section "
+                                                          "(StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder, "
+                                                          "NSMarkovBuilder, NSZongyiBuilder) for --epochs (default "
+                                                          "trainer.max_epochs) whole epochs, validating on the held-out split after "
+                                                          "each; the Markov routine's epoch 0 only accumulates its normaliser"),
           device: Optional[str] = Option(None, hidden=True)):
     """Train: build the routine from CONFIG (+ `a.b=c` overrides) and run fused optimisation steps."""
     cfg = load_config(str(config_path), overrides or [])
@@ -469,8 +510,8 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
          map_location: Optional[str] = None, debug: bool = False, no_logging: bool = False,
          batches: int = Option(1, help="test batches to average over"), data: Optional[Path] = None,
          batch_size: Optional[int] = None, grid: int = 64, size: Optional[List[int]] = None,
-         builder: bool = Option(False, "--builder", help="mesh and point-cloud routines: the loss over the whole test split of the "
-                                                         "config's `builder` section"),
+         builder: bool = Option(False, "--builder", help="the test metrics over the whole test split of the config's `builder` "
+                                                         "section"),
          device: Optional[str] = Option(None, hidden=True)):
     """Test: load the best checkpoint of the trial (or `checkpoint_path=...` override) and report the test metrics."""
     if builder and data is not None:
@@ -484,9 +525,12 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
     routine.to(dev)
     routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
     if builder:
-        test_set = _instantiate_builder(cfg, kind, batch_size).test_data(dev)
-        print(json.dumps(dict(checkpoint=str(ckpt), test_loss=round(_split_loss(routine, test_set), 6), samples=test_set.n)),
-              flush=True)
+        test_set = _instantiate_builder(cfg, kind, batch_size, routine).test_data(dev)
+        if kind in TEST_KEYS:
+            m = _split_loss(routine, test_set, "test_step", TEST_KEYS[kind])
+        else:
+            m = dict(test_loss=_split_loss(routine, test_set)["valid_loss"])
+        print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in m.items()}, samples=test_set.n)), flush=True)
         return
     src = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial)
     it = iter(src)
@@ -510,10 +554,17 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
             map_location: Optional[str] = None, debug: bool = False,
             n_steps: Optional[int] = Option(None, help="rollout length (default: the routine's n_steps)"),
             output: Optional[Path] = Option(None, help="write the predictions here (.npz); default: <trial dir>/predictions.npz"),
-            data: Optional[Path] = None, batch_size: Optional[int] = 1, grid: int = 64, size: Optional[List[int]] = None,
+            data: Optional[Path] = None,
+            batch_size: Optional[int] = Option(None, help="default 1; with --builder: trajectories per chunk, default all at once"),
+            grid: int = 64, size: Optional[List[int]] = None,
+            builder: bool = Option(False, "--builder", help="Markov and rollout routines: predict on the `inference_data()` of the "
+                                                            "config's `builder` section (the first 512 trajectories of its file) "
+                                                            "and report the reference's `inference_time`"),
             device: Optional[str] = Option(None, hidden=True)):
     """Predict: load the best checkpoint, run the model autoregressively (grid routines) or once (mesh routine), save the
     predictions and report the time per model step (the reference's `inference_time`, commands/train.py:132-148)."""
+    if builder and data is not None:
+        raise ValueError("--builder takes the trajectories from the config's builder section: it does not go with --data")
     cfg = load_config(str(config_path), overrides or [])
     dev = _device(device)
     routine = build_routine(cfg).to(dev)
@@ -522,10 +573,26 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     routine.load_lightning_model_state(str(ckpt), map_location)
     routine.to(dev)
     routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
-    b = next(iter(_Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial)))
+    traj = None
+    if builder:
+        if kind not in TEST_KEYS:
+            raise ValueError("predict --builder runs the Markov and rollout routines (NSMarkovBuilder, NSZongyiBuilder), whose "
+                             "builders have inference_data()")
+        traj = _instantiate_builder(cfg, kind, None, routine).inference_data(dev)["data"]
+        chunk = batch_size or len(traj)
+        if chunk < 1:
+            raise ValueError("--batch-size is at least 1")
+    else:
+        b = next(iter(_Batches(routine, cfg, dev, data, batch_size or 1, grid, size, seed=7231 + trial)))
 
     def run():
         with torch.no_grad():
+            if traj is not None:      # commands/train.py:134-143: routine.infer over the trajectories, here --batch-size at a time
+                parts = []
+                for lo in range(0, len(traj), chunk):
+                    part = {"data": traj[lo:lo + chunk]}
+                    parts.append(routine._valid_step(part)[2] if kind == "markov" else routine.forward(part)[2])
+                return parts[0] if len(parts) == 1 else torch.cat(parts)
             if kind == "markov":
                 return routine.rollout(b["x"], n_steps, b.get("f"), b.get("mu"))
             if kind == "rollout":
@@ -546,8 +613,13 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     steps = (n_steps or getattr(routine, "n_steps", None) or 1) if kind not in ("mesh", "pointcloud") else 1
     out = output or (ckpt.parent / "predictions.npz")
     np.savez(str(out), preds=preds.detach().cpu().numpy())
+    extra = {}
+    if traj is not None:      # the reference's own figure: seconds per trajectory and unit of simulated time (commands/train.py:144-148)
+        steps = routine.n_steps or traj.shape[-1] - 1
+        extra = dict(samples=len(traj), n_steps=steps, step_size=routine.step_size, elapsed=elapsed,
+                     inference_time=elapsed / len(traj) / (routine.step_size * steps))
     print(json.dumps(dict(checkpoint=str(ckpt), predictions=str(out), shape=list(preds.shape),
-                          inference_time_ms_per_step=round(1e3 * elapsed / steps, 4))), flush=True)
+                          inference_time_ms_per_step=round(1e3 * elapsed / steps, 4), **extra)), flush=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------

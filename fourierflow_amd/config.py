@@ -6,8 +6,8 @@ The reference composes ``experiments/**/config.yaml`` with Hydra, resolves the c
 drives the hot path -- ``routine`` with its ``conv`` / ``model``, ``optimizer`` and ``scheduler`` nodes -- and
 maps ``fourierflow.*`` targets onto their MI355X-native mirrors, so an unmodified torus_li config builds
 the HIP-backed routine.  ``build_routine`` leaves the other sections alone; of them the CLI's ``--builder`` instantiates a
-``builder`` section that names StructuredMesh2DBuilder, PlasticityBuilder or ElasticityBuilder (builders/mesh_data.py) and
-reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
+``builder`` section that names StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder (builders/mesh_data.py),
+NSMarkovBuilder or NSZongyiBuilder (builders/ns_data.py) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
 scope).
 """
 from __future__ import annotations
@@ -41,6 +41,8 @@ TARGET_MAP = {
     "fourierflow.builders.StructuredMesh2DBuilder": "fourierflow_amd.builders.StructuredMesh2DBuilder",
     "fourierflow.builders.PlasticityBuilder": "fourierflow_amd.builders.PlasticityBuilder",
     "fourierflow.builders.ElasticityBuilder": "fourierflow_amd.builders.ElasticityBuilder",
+    "fourierflow.builders.NSMarkovBuilder": "fourierflow_amd.builders.NSMarkovBuilder",
+    "fourierflow.builders.NSZongyiBuilder": "fourierflow_amd.builders.NSZongyiBuilder",
 }
 _INTERP = re.compile(r"^\$\{\s*([\w.]+)\s*:\s*(.*?)\s*\}$")
 

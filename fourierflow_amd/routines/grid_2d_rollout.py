@@ -58,11 +58,14 @@ class Grid2DRolloutExperiment(CheckpointMixin, nn.Module):
         return torch.stack([tx[:, None].expand(X, Y), ty[None, :].expand(X, Y)], dim=-1)[None].expand(B, X, Y, 2)
 
     def forward(self, data):
-        """data['data'] [B, X, Y, 10 + n_steps] -> the tuple of ``_learning_step`` (:38-50)."""
-        xx = data['data'][..., :10]
+        """data['data'] [B, X, Y, 10 + n_steps] -> the tuple of ``_learning_step`` (:38-50).  The reference's input window of 10
+        fields is its model's ``input_dim`` of 12 less the two position channels; a model of another ``input_dim`` takes that
+        many."""
+        n_in = int(getattr(self.conv, "input_dim", 12)) - 2
+        xx = data['data'][..., :n_in]
         B, X, Y, _ = xx.shape
         xx = torch.cat([xx, self._positions(B, X, Y, xx.device)], dim=-1)
-        return self._learning_step({'x': xx, 'y': data['data'][..., 10:]})
+        return self._learning_step({'x': xx, 'y': data['data'][..., n_in:]})
 
     def _learning_step(self, batch):
         xx, yy = batch['x'], batch['y']
