@@ -100,6 +100,14 @@ class MarkovExtra(C.Structure):
     _fields_ = [("force", P), ("mu", P), ("use_position", C.c_int32), ("pad_", C.c_int32)]
 
 
+class MarkovAdvanceDesc(C.Structure):
+    """Mirror of ``ffno_markov_advance_desc`` (include/ffno.h)."""
+    _fields_ = [("affine", P), ("prev", P), ("traj", P), ("feats", P), ("derived", P), ("force", P), ("mu", P),
+                ("force_stride", C.c_int64), ("L", C.c_int32), ("col", C.c_int32), ("D", C.c_int32),
+                ("use_position", C.c_int32), ("normalize", C.c_int32), ("low", C.c_float), ("high", C.c_float),
+                ("pad_", C.c_int32)]
+
+
 class PadMap(C.Structure):
     """Mirror of ``ffno_padmap`` (include/ffno.h)."""
     _fields_ = [("size", C.c_int32 * 3), ("padded", C.c_int32 * 3)]
@@ -273,6 +281,7 @@ SIGNATURES = {
     "ffno_markov_traj_ws_floats": (SZ, [I, I, I, I]),
     "ffno_markov_traj_step": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, P]),
     "ffno_markov_traj_metrics": (I, [P, P, I, I, I, I, F, P]),
+    "ffno_markov_advance": (I, [P, P, P, I, I, I, P]),
     "ffno_markov_pairs": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "ffno_sample_gather": (I, [P, I, P, I, I, P]),
     "ffno_adamw_flat":(I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),

@@ -1,7 +1,8 @@
-"""`python -m fourierflow_amd {train,test,predict} CONFIG.yaml [overrides...]` and `python -m fourierflow_amd generate
+"""`python -m fourierflow_amd {train,test,predict} CONFIG.yaml [overrides...]`, `python -m fourierflow_amd rollout CONFIG.yaml
+--init IC.npz` (the trained Markov model as a simulator, see `rollout` below) and `python -m fourierflow_amd generate
 navier-stokes PATH` (the data the 2-D Navier-Stokes configs train on, see `navier_stokes` below) -- the command surface of the reference
-(`fourierflow train | test | predict`, reference commands/train.py:27-148, commands/test.py:24-90,
-commands/predict.py:24-110) for the routines built here, with the same positional arguments and flag names
+(`fourierflow train | test | predict | infer`, reference commands/train.py:27-148, commands/test.py:24-90,
+commands/predict.py:24-110, commands/infer.py) for the routines built here, with the same positional arguments and flag names
 (``--force --resume --checkpoint-id --trial --debug --no-logging --map-location``) and the same on-disk layout:
 
     <config_dir>/checkpoints/trial-<trial>-<id>/epoch=<e>-step=<s>-valid_loss=<v>.ckpt   (best, what `test` / `predict` load)
@@ -620,6 +621,88 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
                      inference_time=elapsed / len(traj) / (routine.step_size * steps))
     print(json.dumps(dict(checkpoint=str(ckpt), predictions=str(out), shape=list(preds.shape),
                           inference_time_ms_per_step=round(1e3 * elapsed / steps, 4), **extra)), flush=True)
+
+
+def _initial_conditions(path: Path, routine) -> Dict[str, np.ndarray]:
+    """x0 [n, M, N] [, f, mu] of an initial-condition file: `x0`, `vorticity` or `data`, as [n, M, N] or -- a trajectory array
+    [n, M, N, T] -- its first time slice."""
+    with np.load(str(path)) as z:
+        name = next((k for k in ("x0", "vorticity", "data") if k in z.files), None)
+        if name is None:
+            raise ValueError(f"{path}: none of the arrays x0, vorticity, data (found {sorted(z.files)})")
+        x0 = z[name].astype(np.float32)
+        if x0.ndim == 4:
+            x0 = x0[..., 0]
+        if x0.ndim != 3:
+            raise ValueError(f"{path}: {name} must be [n, M, N] or [n, M, N, T], got {list(z[name].shape)}")
+        arrays = {"x0": np.ascontiguousarray(x0)}
+        missing = [k for k, on in (("f", routine.append_force), ("mu", routine.append_mu)) if on and k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: arrays {missing} missing (found {sorted(z.files)}): the config appends them to the input")
+        for k, on in (("f", routine.append_force), ("mu", routine.append_mu)):
+            if on:
+                arrays[k] = z[k].astype(np.float32)
+                if len(arrays[k]) != len(x0):
+                    raise ValueError(f"{path}: {k} holds {len(arrays[k])} samples, {name} {len(x0)}")
+    return arrays
+
+
+@app.command()
+def rollout(config_path: Path, overrides: Optional[List[str]] = Argument(None), trial: int = 0,
+            map_location: Optional[str] = None,
+            init: Path = Option(..., help=".npz of initial conditions: x0, vorticity or data as [n, M, N] (a trajectory array "
+                                          "[n, M, N, T] gives its first time slice) [, f [n, M, N] or [n, M, N, >= steps], mu [n]]"),
+            steps: int = Option(100, help="model steps to simulate"),
+            every: int = Option(1, help="keep every N-th state (divides --steps)"),
+            batch_size: Optional[int] = Option(None, help="samples simulated at once; default: the whole file"),
+            output: Optional[Path] = Option(None, help="write preds and times here (.npz); default: <trial dir>/rollout.npz"),
+            device: Optional[str] = Option(None, hidden=True)):
+    """Rollout: load the best checkpoint and run the model as a simulator from the initial conditions of --init (the reference's
+    `fourierflow infer`, commands/infer.py): `preds` [n, M, N, steps / every] and `times` = step_size * every * (1 .. L), one
+    warm-up chunk, then the timed run; reports ms per model step and the reference's `inference_time` (seconds per sample and
+    unit of simulated time)."""
+    cfg = load_config(str(config_path), overrides or [])
+    dev = _device(device)
+    routine = build_routine(cfg).to(dev)
+    if _kind(routine) != "markov":
+        raise ValueError(f"rollout runs the Markov routine (Grid2DMarkovExperiment); this config builds {type(routine).__name__}")
+    if batch_size is not None and batch_size < 1:
+        raise ValueError("--batch-size is at least 1")
+    if steps < 1 or every < 1 or steps % every:
+        raise ValueError(f"--steps is a positive multiple of --every, got --steps {steps} --every {every}")
+    arrays = _initial_conditions(init, routine)
+    ckpt = _best_checkpoint(config_path.parent, trial, cfg.get("checkpoint_path"))
+    routine.load_lightning_model_state(str(ckpt), map_location)
+    routine.to(dev)
+    routine.eval()
+    n = len(arrays["x0"])
+    chunk = min(batch_size or n, n)
+    on_dev = {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
+
+    def run(lo):
+        part = {k: v[lo:lo + chunk] for k, v in on_dev.items()}
+        return routine.simulate(part["x0"], steps, part.get("f"), part.get("mu"), every=every)
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+
+    run(0)      # warm-up: workspaces, weight packs
+    sync()
+    t0 = time.perf_counter()
+    parts = [run(lo) for lo in range(0, n, chunk)]
+    sync()
+    elapsed = time.perf_counter() - t0
+    preds = parts[0] if len(parts) == 1 else torch.cat(parts)
+    finite = bool(torch.isfinite(preds[..., -1]).all().item())      # the final field: one host read
+    out = output or (ckpt.parent / "rollout.npz")
+    L = preds.shape[-1]
+    np.savez(str(out), preds=preds.cpu().numpy(),
+             times=(routine.step_size * every * np.arange(1, L + 1)).astype(np.float32))
+    print(json.dumps(dict(checkpoint=str(ckpt), predictions=str(out), shape=list(preds.shape), steps=steps, every=every,
+                          samples=n, batch=chunk, step_size=routine.step_size, elapsed=elapsed,
+                          ms_per_step=round(1e3 * elapsed / (steps * len(parts)), 4), finite=finite,
+                          inference_time=elapsed / n / (routine.step_size * steps))), flush=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------

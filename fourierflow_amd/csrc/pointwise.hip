@@ -425,7 +425,13 @@ struct MarkovSrc {
     const float* force;   // [B][M][N] or null   (append_force, :156-158)
     const float* mu;      // [B] or null         (append_mu, :160-162)
     int Cx, use_pos;
+    long fstride;         // elements between two pixels of `force`: 1 = a [B][M][N] map, T' = one column of a [B][M][N][T'] stack
 };
+
+// the one place a raw feature becomes a normalised one: every kernel that writes features goes through it
+__device__ __forceinline__ float markov_normalized(float v, const float* derived, int c, int D) {
+    return (v - derived[c]) / derived[D + c];
+}
 
 __device__ __forceinline__ float markov_raw(const MarkovSrc& src, long p, int c, int M, int N, float low, float high) {
     if (c < src.Cx) return src.x[p * src.Cx + c];
@@ -439,7 +445,7 @@ __device__ __forceinline__ float markov_raw(const MarkovSrc& src, long p, int c,
         c -= 2;
     }
     if (src.force) {
-        if (c == 0) return src.force[p];
+        if (c == 0) return src.force[p * src.fstride];
         c -= 1;
     }
     return src.mu[p / ((long)M * N)];
@@ -514,9 +520,45 @@ __global__ __launch_bounds__(256) void markov_features_kernel(MarkovSrc src, con
         const long p = e / D;
         const int c = (int)(e % D);
         float v = markov_raw(src, p, c, M, N, low, high);
-        if (normalize) v = (v - derived[c]) / derived[D + c];
+        if (normalize) v = markov_normalized(v, derived, c, D);
         if (noise) v = fmaf(noise[e], noise_std, v);
         out[e] = v;
+    }
+}
+
+// ---- Markov rollout feedback --------------------------------------------------------------------------------
+// One launch per rollout step: a thread turns the model output of a pixel into the prediction P, writes it to the running field
+// (which may be `prev` or `out` itself: the pixel's inputs are read before anything of it is written, and no other thread touches
+// it), to its trajectory column, and writes the D normalised features of the next step -- channel 0 is P, the others are the
+// markov_raw() channels with Cx = 1, through markov_normalized() with the statistics that stand still during a rollout.
+struct MarkovAdvance {
+    const float* out;
+    const float* affine;
+    const float* prev;
+    float* field;
+    float* traj;
+    float* feats;
+    const float* derived;
+    MarkovSrc src;        // x is never read: channel 0 comes from the register
+    long P;
+    int M, N, L, col, D, normalize;
+    float low, high;
+};
+
+__global__ __launch_bounds__(256) void markov_advance_kernel(MarkovAdvance a) {
+    const float sc = a.affine ? a.affine[0] : 1.f, sh = a.affine ? a.affine[1] : 0.f;   // Normalizer.inverse(channel=0)
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < a.P; q += (long)gridDim.x * 256) {
+        const float raw = a.affine ? fmaf(a.out[q], sc, sh) : a.out[q];
+        const float P = a.prev ? a.prev[q] + raw : raw;
+        a.field[q] = P;
+        if (a.traj) a.traj[q * a.L + a.col] = P;
+        if (a.feats) {
+            float* f = a.feats + q * a.D;
+            for (int c = 0; c < a.D; ++c) {
+                const float v = c == 0 ? P : markov_raw(a.src, q, c, a.M, a.N, a.low, a.high);
+                f[c] = a.normalize ? markov_normalized(v, a.derived, c, a.D) : v;
+            }
+        }
     }
 }
 
@@ -1060,7 +1102,7 @@ extern "C" int ffno_markov_features(const float* x, float* state, float* derived
                                     float noise_std, float eps, int accumulate, int normalize,
                                     const ffno_markov_extra* extra, void* stream) {
     if (!x || !out || !state || !derived || !partial || B <= 0 || M <= 0 || N <= 0 || Cx <= 0) return FFNO_EINVAL;
-    MarkovSrc src{x, extra ? extra->force : nullptr, extra ? extra->mu : nullptr, Cx, extra ? extra->use_position : 1};
+    MarkovSrc src{x, extra ? extra->force : nullptr, extra ? extra->mu : nullptr, Cx, extra ? extra->use_position : 1, 1L};
     const int D = Cx + (src.use_pos ? 2 : 0) + (src.force ? 1 : 0) + (src.mu ? 1 : 0);
     if (D > 16) return FFNO_EUNSUPPORTED;
     const long P = (long)B * M * N;
@@ -1107,6 +1149,42 @@ extern "C" int ffno_markov_traj_metrics(const float* sums, float* metrics, int B
     if ((long)M * N > 0x7fffffffL) return FFNO_EUNSUPPORTED;
     FFNO_LAUNCH(markov_traj_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sums, metrics, B, lploss_slices(M * N),
                 n_steps, threshold);
+    return pw_status();
+}
+
+// (two pixels per thread, so that the loads of the second overlap the stores of the first; at most 1024 workgroups)
+extern "C" int ffno_markov_advance(const float* out, float* field, const ffno_markov_advance_desc* desc, int B, int M, int N,
+                                   void* stream) {
+    if (!out || !field || B <= 0 || M <= 0 || N <= 0) return FFNO_EINVAL;
+    MarkovAdvance a{};
+    a.out = out;
+    a.field = field;
+    a.P = (long)B * M * N;
+    a.M = M;
+    a.N = N;
+    if (desc) {
+        if (desc->traj && (desc->L <= 0 || desc->col < 0 || desc->col >= desc->L)) return FFNO_EINVAL;
+        if (desc->normalize && !desc->derived) return FFNO_EINVAL;
+        if (desc->force && desc->force_stride < 1) return FFNO_EINVAL;
+        if (desc->feats) {
+            const int D = 1 + (desc->use_position ? 2 : 0) + (desc->force ? 1 : 0) + (desc->mu ? 1 : 0);
+            if (desc->D != D || D > 16) return FFNO_EINVAL;
+        }
+        a.affine = desc->affine;
+        a.prev = desc->prev;
+        a.traj = desc->traj;
+        a.feats = desc->feats;
+        a.derived = desc->derived;
+        a.src = MarkovSrc{nullptr, desc->force, desc->mu, 1, desc->use_position, (long)desc->force_stride};
+        a.L = desc->L;
+        a.col = desc->col;
+        a.D = desc->D;
+        a.normalize = desc->normalize;
+        a.low = desc->low;
+        a.high = desc->high;
+    }
+    const unsigned blocks = (unsigned)max(1L, min((a.P + 511) / 512, 1024L));
+    FFNO_LAUNCH(markov_advance_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
     return pw_status();
 }
 

@@ -229,6 +229,92 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         self.normalizer.train(was_training)
         return torch.cat(preds, dim=-1)
 
+    @torch.no_grad()
+    def simulate(self, x0: torch.Tensor, n_steps: int, f: Optional[torch.Tensor] = None, mu: Optional[torch.Tensor] = None,
+                 every: int = 1) -> torch.Tensor:
+        """The trained model as a simulator: n_steps autoregressive steps from x0 [B, M, N] (or [B, M, N, 1]), every `every`-th
+        state kept -> [B, M, N, n_steps / every] (column j is the state after (j + 1) * every steps; n_steps is a multiple of
+        `every`, so that the columns are evenly spaced in time).  ``f`` is one force map [B, M, N] or a stack [B, M, N, T' >=
+        n_steps] whose column t drives step t (read in place, strided); ``mu`` is [B].
+
+        The feature kernel runs once, on x0, in eval mode: the statistics stand still.  Every step is then the inference engine
+        and ONE ffno_markov_advance launch (inverse normalisation, difference update, the running field in place, the trajectory
+        column, the next step's features written straight into the engine's input buffer).  The trajectory is allocated once.
+        With `use_velocity` or `shuffle_grid` the launch only updates the field and the trajectory, and the velocity / feature
+        / gather launches of `_valid_step` build the next input from the field.  The numbers are those of `_valid_step`, bit
+        for bit: the same engine on the same inputs, the same fused order of the inverse affine."""
+        n_steps, every = int(n_steps), int(every)
+        if n_steps < 1 or every < 1 or n_steps % every:
+            raise ValueError(f"simulate needs n_steps >= 1 and every >= 1 dividing n_steps, got n_steps={n_steps}, every={every}")
+        _lib.require_device_tensor(x0, "x0")
+        if x0.dim() == 4 and x0.shape[-1] == 1:
+            x0 = x0[..., 0]
+        if x0.dim() != 3:
+            raise ValueError(f"x0 must be [B, M, N] or [B, M, N, 1], got {tuple(x0.shape)}")
+        B, M, N = x0.shape
+        dev, lib, stream = x0.device, _lib.get_lib(), _lib.current_stream(x0.device)
+        force = mu_t = None
+        if self.append_force:
+            if f is None or f.dim() not in (3, 4) or tuple(f.shape[:3]) != (B, M, N) or (f.dim() == 4 and f.shape[-1] < n_steps):
+                raise ValueError(f"f must be [{B}, {M}, {N}] or [{B}, {M}, {N}, >= {n_steps}], got "
+                                 f"{None if f is None else tuple(f.shape)}")
+            _lib.require_device_tensor(f, "f")
+            force = f.float()
+            # a pixel-uniform stride is all the kernel needs: a slice of a contiguous stack along time is read where it lies
+            s = force.stride(2) if force.dim() == 4 else 1
+            if force.dim() == 3 or s < 1 or tuple(force.stride()[:3]) != (M * N * s, N * s, s):
+                force = force.contiguous()
+        if self.append_mu:
+            if mu is None or tuple(mu.shape) != (B,):
+                raise ValueError(f"mu must be [{B}], got {None if mu is None else tuple(mu.shape)}")
+            _lib.require_device_tensor(mu, "mu")
+            mu_t = mu.contiguous().float()
+        stack = force is not None and force.dim() == 4
+        f_stride = force.stride(2) if stack else 1
+
+        def f_at(t):      # the map of step t as `_build_features` takes it
+            return force[..., t].contiguous() if stack else force
+
+        def f_ptr(t):
+            if force is None:
+                return None
+            return force.data_ptr() + 4 * t * force.stride(3) if stack else force.data_ptr()
+
+        field = torch.empty(B, M, N, 1, dtype=torch.float32, device=dev)      # the running field, updated in place
+        field.copy_(x0.unsqueeze(-1))
+        traj = torch.empty(B, M, N, n_steps // every, dtype=torch.float32, device=dev)
+        fused = not (self.use_velocity or self.shuffle_grid)
+        tr = self.trainer()
+        view = {"own_output": False} if getattr(tr.engine, "can_return_view", False) else {}
+        D = self.conv.input_dim
+        was_training = self.normalizer.training
+        self.normalizer.eval()
+        try:
+            feats = self._build_features({'x': field, 'f': f_at(0) if force is not None else None, 'mu': mu_t}, add_noise=False)
+            affine = self._affine_tensor()
+            desc = _capi.MarkovAdvanceDesc(affine=_p(affine), prev=_p(field) if self.learn_difference else None,
+                                           derived=_p(self._derived), mu=_p(mu_t), force_stride=f_stride,
+                                           L=traj.shape[-1], D=D, use_position=int(self.use_position),
+                                           normalize=int(self.should_normalize), low=float(self.low), high=float(self.high))
+            for t in range(n_steps):
+                if not fused and t > 0:
+                    feats = self._build_features({'x': field, 'f': f_at(t) if force is not None else None, 'mu': mu_t},
+                                                 add_noise=False)
+                if fused:      # (the engine's own output buffer: the launch below consumes it before the next pass)
+                    out = tr.engine.forward(feats, False, **view)
+                else:
+                    out = self._unshuffle(tr.engine.forward(self._shuffle(feats), False))
+                if tuple(out.shape) != (B, M, N, 1):
+                    raise ValueError(f"the rollout feeds one predicted channel back, conv returned {tuple(out.shape)}")
+                keep = (t + 1) % every == 0
+                desc.traj, desc.col = (_p(traj) if keep else None), ((t + 1) // every - 1 if keep else 0)
+                build = fused and t + 1 < n_steps
+                desc.feats, desc.force = (_p(feats) if build else None), (f_ptr(t + 1) if build else None)
+                _capi.check(lib.ffno_markov_advance(_p(out), _p(field), ctypes.byref(desc), B, M, N, stream), "markov_advance")
+        finally:
+            self.normalizer.train(was_training)
+        return traj
+
     # -- trajectory validation (grid_2d_markov.py:195-416) ---------------------------------------------------------------------
     def _traj_geometry(self, data: torch.Tensor):
         B, M, N, T = data.shape

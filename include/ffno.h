@@ -39,6 +39,13 @@
  *   Half the activation bytes of a training step; the price is the bf16 rounding of the stored tensors (forward ~3e-3
  *   relative against the fp32 path over 24 layers: a throughput variant with its own tolerance, never the parity path).
  *
+ * Rollouts (a trained F-FNO used as a simulator: Grid2DMarkovExperiment.simulate, `python -m fourierflow_amd rollout`)
+ *   One step is the inference engine (ffno_lift_fwd, ffno_layer_infer / ffno_infer_stack, ffno_head_fwd) and ONE feedback launch,
+ *   ffno_markov_advance: inverse normalisation, difference update, the running field in place, the trajectory column and the
+ *   normalised features of the next step.  ffno_markov_features runs once, on the initial condition; the statistics it leaves
+ *   in `derived` stand still for the whole rollout.  The `use_velocity` and `shuffle_grid` inputs are not fused: there the
+ *   launch is called without `feats` and ffno_velocity_features / ffno_markov_features build the next input from the field.
+ *
  * Spectrum layout (internal but part of the ABI because callers own the workspaces):
  *   spec[k][r][ri][c]   k = mode (0..K-1), r = line index, ri = 0 real / 1 imag, c = channel
  *   lines: axis 0 (transform along N, fourier_weight[0]): r = b*M + m  (R = B*M lines of length N)
@@ -873,6 +880,41 @@ int ffno_markov_traj_step(const float* out, const float* affine, const float* pr
                           float* preds, float* sums, int B, int M, int N, int T, int n_steps, int t, void* stream);
 int ffno_markov_traj_metrics(const float* sums, float* metrics, int B, int M, int N, int n_steps, float threshold,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Feedback of one rollout step of the Markov routine (the loop body of routines/grid_2d_markov.py:263-321 between two forward
+ * passes), one launch, fp32, no atomics, every output element written exactly once.  With q = (b, m, n):
+ *   raw      = affine ? fma(out[q], affine[0], affine[1]) : out[q]     (the {std[0], mean[0]} pair of ffno_markov_traj_step)
+ *   P        = prev ? prev[q] + raw : raw                              (prev given = learn_difference)
+ *   field[q] = P                                                       (field may be `prev` or `out` itself)
+ *   traj     : traj[q L + col] = P                                     (traj [B][M][N][L]; NULL = not stored)
+ *   feats    : feats[q D + c], c in [0, D) = normalize ? (v - derived[c]) / derived[D + c] : v  with
+ *              v = P for c = 0, else channel c of ffno_markov_features with Cx = 1: position (use_position) | force | mu
+ * `derived` is the {mean[D], std[D]} buffer ffno_markov_features leaves behind; the non-vorticity channels and the normalisation
+ * are the device code of that kernel, so  feats == ffno_markov_features(field, accumulate = 0)  bit for bit.
+ * `force` is read at force[q force_stride]: stride 1 is a [B][M][N] map, stride T' with force = stack + t is column t of a
+ * [B][M][N][T'] stack (no copy per step).  desc = NULL: field = out and nothing else.
+ * ALIASING: `traj` and `feats` must not overlap any input (out, prev, force, mu, derived, affine) nor `field` nor each other:
+ * a pixel's feats are written while other pixels' inputs are still being read.
+ * FFNO_EINVAL: NULL out / field, a non-positive size, traj with col outside [0, L), feats with D != 1 + 2 use_position +
+ * (force given) + (mu given) or D > 16, normalize without derived, force with force_stride < 1.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct ffno_markov_advance_desc {
+    const float* affine;  /* device float[2] {scale, shift} or NULL */
+    const float* prev;    /* [B][M][N] or NULL */
+    float* traj;          /* [B][M][N][L] or NULL */
+    float* feats;         /* [B][M][N][D] or NULL */
+    const float* derived; /* {mean[D], std[D]}; required with normalize */
+    const float* force;   /* or NULL */
+    const float* mu;      /* [B] or NULL */
+    int64_t force_stride;
+    int32_t L, col, D;
+    int32_t use_position, normalize;
+    float low, high;      /* linspace ends of the position channels */
+    int32_t pad_;
+} ffno_markov_advance_desc;
+int ffno_markov_advance(const float* out, float* field, const ffno_markov_advance_desc* desc, int B, int M, int N,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training batches of the Markov routine drawn from whole trajectories on the device: what indexing the reference's
