@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 7
+ABI_VERSION = 8
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -283,6 +283,7 @@ SIGNATURES = {
     "ffno_markov_traj_metrics": (I, [P, P, I, I, I, I, F, P]),
     "ffno_markov_advance": (I, [P, P, P, I, I, I, P]),
     "ffno_markov_pairs": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
+    "ffno_markov_pairs_tf": (I, [P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, I, P]),
     "ffno_sample_gather": (I, [P, I, P, I, I, P]),
     "ffno_adamw_flat":(I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),
     "ffno_adam_flat": (I, [P, P, P, P, SZ, F, F, F, F, F, I, F, P]),

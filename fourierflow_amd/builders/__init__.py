@@ -2,9 +2,11 @@
 training set of the Markov routine (``MarkovTrajectoryData``: the pair datasets of ns_markov.py / kolmogorov.py drawn on the
 device from whole trajectories); and the dataset builders of the mesh and point-cloud experiments (``StructuredMesh2DBuilder``,
 ``PlasticityBuilder``, ``ElasticityBuilder``: the datasets' own files, split as the reference splits them, held on the device as
-``DeviceSampleData``) and of the torus_li experiments (``NSMarkovBuilder``, ``NSZongyiBuilder``: builders/ns_data.py).  Without a builder the training commands read ``.npz`` files directly (fourierflow_amd/cli.py)."""
+``DeviceSampleData``), of the torus_li experiments (``NSMarkovBuilder``, ``NSZongyiBuilder``: builders/ns_data.py) and of the
+contextual torus_vis / torus_vis_force experiments (``NSContextualBuilder``: builders/ns_contextual.py).  Without a builder the training commands read ``.npz`` files directly (fourierflow_amd/cli.py)."""
 from .markov_data import MarkovTrajectoryData  # noqa: F401
 from .mesh_data import ElasticityBuilder, PlasticityBuilder, StructuredMesh2DBuilder  # noqa: F401
+from .ns_contextual import NSContextualBuilder  # noqa: F401
 from .ns_data import NSMarkovBuilder, NSZongyiBuilder  # noqa: F401
 from .sample_data import DeviceSampleData  # noqa: F401
 from .synthetic import Force, GaussianRF, random_force, solve_navier_stokes_2d  # noqa: F401

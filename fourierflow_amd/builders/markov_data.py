@@ -2,15 +2,17 @@
 ``DataLoader(shuffle=True, drop_last=False)`` over ``NavierStokesTrainingDataset`` (builders/ns_markov.py:36-41, 62-91) and over
 ``KolmogorovTorchDataset`` (builders/kolmogorov.py:111-139), without the expanded copies those datasets hold.
 
-``data [n, M, N, T]`` (and ``f [n, M, N]`` / ``mu [n]``) are uploaded once, in the layout of the files.  A pair id
+``data [n, M, N, T]`` (and ``f [n, M, N]`` or ``f [n, M, N, T]`` / ``mu [n]``) are uploaded once, in the layout of the files.  A pair id
 ``p = b P + j`` names trajectory ``b`` and input time ``t = t0 + j``:
 
     mode "ns_markov":   t0 = k, P = T - 2 k    x = data[b, ..., t], y = data[b, ..., t + k], dx = x - data[b, ..., t - k], dy = y - x
     mode "kolmogorov":  t0 = 0, P = T - k      x, y only
 
-(k = 1 in ``ns_markov`` mode is the reference's dataset.)  An epoch is a permutation of the ``n P`` ids, uploaded once as int32;
-each batch is ONE ``ffno_markov_pairs`` launch that reads its ids through a pointer into that array, so a step costs no host
-work beyond the launch.
+(k = 1 in ``ns_markov`` mode is the reference's dataset.)  A force with one map per snapshot, ``f [n, M, N, T]``, gives the pair
+the map of its TARGET time, ``batch['f'] = f[b, ..., t + k]`` (NavierStokesTrainingDataset of builders/ns_contextual.py:63-66);
+either way ``batch['f']`` is ``[B, M, N]``.  An epoch is a permutation of the ``n P`` ids, uploaded once as int32; each batch is
+ONE ``ffno_markov_pairs_tf`` launch (``ffno_markov_pairs`` with the force's time axis) that reads its ids through a pointer into
+that array, so a step costs no host work beyond the launch.
 
 Order.  ``shuffle=False`` is the reference's ``(b t)`` order, p = 0, 1, 2, ...  ``shuffle=True`` draws ``torch.randperm(n P)``
 once per epoch from a CPU ``torch.Generator`` seeded once with ``seed`` (consecutive draws: the same seed gives the same run).
@@ -78,10 +80,13 @@ class MarkovTrajectoryData:
             raise ValueError(f"{n} x {self.P} pairs do not fit the kernel's int32 ids")
         self.data = _upload(data, self.device)
         self.f = self.mu = None
+        self.Tf = 0      # force maps per trajectory along f's last axis; 0: one map
         if f is not None:
             f = _tensor(f, "f")
-            if tuple(f.shape) != (n, M, N):
-                raise ValueError(f"f must be one force map per trajectory {(n, M, N)}, got {tuple(f.shape)}")
+            if tuple(f.shape) not in ((n, M, N), (n, M, N, T)):
+                raise ValueError(f"f must be one force map per trajectory {(n, M, N)} or one per snapshot {(n, M, N, T)}, got "
+                                 f"{tuple(f.shape)}")
+            self.Tf = T if f.dim() == 4 else 0
             self.f = _upload(f, self.device)
         if mu is not None:
             mu = _tensor(mu, "mu")
@@ -142,8 +147,9 @@ class MarkovTrajectoryData:
         def p(t):
             return None if t is None else ctypes.c_void_p(t.data_ptr())
 
-        rc = _lib.get_lib().ffno_markov_pairs(p(self.data), ctypes.c_void_p(ids.data_ptr() + 4 * offset), p(b["x"]), p(b["y"]),
-                                              p(b.get("dx")), p(b.get("dy")), p(self.f), p(b.get("f")), p(self.mu), p(b.get("mu")),
-                                              self.n, M, N, self.T, self.t0, self.k, self.P, B, _lib.current_stream(dev))
+        rc = _lib.get_lib().ffno_markov_pairs_tf(p(self.data), ctypes.c_void_p(ids.data_ptr() + 4 * offset), p(b["x"]), p(b["y"]),
+                                                 p(b.get("dx")), p(b.get("dy")), p(self.f), self.Tf, p(b.get("f")), p(self.mu),
+                                                 p(b.get("mu")), self.n, M, N, self.T, self.t0, self.k, self.P, B,
+                                                 _lib.current_stream(dev))
         _capi.check(rc, "markov_pairs")
         return b

@@ -21,10 +21,12 @@ configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless
 
 ``train CONFIG --builder`` and ``test CONFIG --builder`` run the routines the way the reference does: on the dataset files of the
 config's ``builder`` section (StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder: builders/mesh_data.py; NSMarkovBuilder,
-NSZongyiBuilder: builders/ns_data.py), split by ``train_size`` / ``valid_size`` / ``test_size``, in shuffled epochs drawn on the
+NSZongyiBuilder: builders/ns_data.py; NSContextualBuilder: builders/ns_contextual.py), split by ``train_size`` / ``valid_size`` /
+``test_size`` (NSContextualBuilder: by its train / valid / test files), in shuffled epochs drawn on the
 device, with the validation split evaluated after every epoch and the best checkpoint kept.  For the Markov routine epoch 0 is
 the reference's statistics epoch: one whole pass that only accumulates the normaliser.  ``predict CONFIG --builder`` runs on the
-builder's ``inference_data()`` and reports the reference's ``inference_time``.
+builder's ``inference_data()`` and reports the reference's ``inference_time``; NSContextualBuilder has none, in the reference
+either, and is refused there.
 """
 from __future__ import annotations
 
@@ -175,13 +177,13 @@ def _trajectory_batches(routine, cfg, dev, path: Path, batch_size: Optional[int]
 
 # the classes `--builder` runs and the routine each one feeds
 BUILDERS = {"StructuredMesh2DBuilder": "mesh", "PlasticityBuilder": "mesh", "ElasticityBuilder": "pointcloud",
-            "NSMarkovBuilder": "markov", "NSZongyiBuilder": "rollout"}
+            "NSMarkovBuilder": "markov", "NSZongyiBuilder": "rollout", "NSContextualBuilder": "markov"}
 _ROUTINES = {"mesh": "StructuredMeshExperiment", "pointcloud": "PointCloudExperiment", "markov": "Grid2DMarkovExperiment",
              "rollout": "Grid2DRolloutExperiment"}
 
 
 def _instantiate_builder(cfg, kind: str, batch_size: Optional[int], routine=None):
-    """The config's `builder` section as one of builders/mesh_data.py / ns_data.py (`${oc.env:DATA_ROOT}` resolved like everywhere
+    """The config's `builder` section as one of builders/mesh_data.py / ns_data.py / ns_contextual.py (`${oc.env:DATA_ROOT}` resolved like everywhere
     else).  A section that names another builder than the routine's, none at all, or lacks an argument its class requires is
     refused before anything is read."""
     import inspect
@@ -202,6 +204,8 @@ def _instantiate_builder(cfg, kind: str, batch_size: Optional[int], routine=None
     if batch_size:
         node["batch_size"] = batch_size
     bld = instantiate(node)
+    if routine is not None and hasattr(bld, "append_force"):      # f / mu go along when the routine appends them
+        bld.append_force, bld.append_mu = bool(routine.append_force), bool(routine.append_mu)
     if kind == "rollout" and routine is not None and \
             (bld.n_steps != routine.n_steps or bld.append_pos != bool(routine.append_pos)):
         raise ValueError(f"builder n_steps = {bld.n_steps}, append_pos = {bld.append_pos} but the routine rolls out n_steps = "
@@ -392,7 +396,7 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
                                                        "default) or kolmogorov (inputs 0 ... T-1-k)"),
           builder: bool = Option(False, "--builder", help="train on the dataset files of the config's `builder` section "
                                                           "(StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder, "
-                                                          "NSMarkovBuilder, NSZongyiBuilder) for --epochs (default "
+                                                          "NSMarkovBuilder, NSZongyiBuilder, NSContextualBuilder) for --epochs (default "
                                                           "trainer.max_epochs) whole epochs, validating on the held-out split after "
                                                           "each; the Markov routine's epoch 0 only accumulates its normaliser"),
           device: Optional[str] = Option(None, hidden=True)):
@@ -579,7 +583,12 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
         if kind not in TEST_KEYS:
             raise ValueError("predict --builder runs the Markov and rollout routines (NSMarkovBuilder, NSZongyiBuilder), whose "
                              "builders have inference_data()")
-        traj = _instantiate_builder(cfg, kind, None, routine).inference_data(dev)["data"]
+        bld = _instantiate_builder(cfg, kind, None, routine)
+        if not hasattr(bld, "inference_data"):
+            raise ValueError(f"predict --builder runs on a builder's inference_data(), and {type(bld).__name__} has none -- the "
+                             f"reference gives it none either (builders/ns_contextual.py): use `test --builder` for its test "
+                             f"split, or `rollout --init FILE` to run the model as a simulator")
+        traj = bld.inference_data(dev)["data"]
         chunk = batch_size or len(traj)
         if chunk < 1:
             raise ValueError("--batch-size is at least 1")

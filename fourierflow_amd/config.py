@@ -7,7 +7,7 @@ drives the hot path -- ``routine`` with its ``conv`` / ``model``, ``optimizer`` 
 maps ``fourierflow.*`` targets onto their MI355X-native mirrors, so an unmodified torus_li config builds
 the HIP-backed routine.  ``build_routine`` leaves the other sections alone; of them the CLI's ``--builder`` instantiates a
 ``builder`` section that names StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder (builders/mesh_data.py),
-NSMarkovBuilder or NSZongyiBuilder (builders/ns_data.py) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
+NSMarkovBuilder, NSZongyiBuilder (builders/ns_data.py) or NSContextualBuilder (builders/ns_contextual.py) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
 scope).
 """
 from __future__ import annotations
@@ -43,6 +43,7 @@ TARGET_MAP = {
     "fourierflow.builders.ElasticityBuilder": "fourierflow_amd.builders.ElasticityBuilder",
     "fourierflow.builders.NSMarkovBuilder": "fourierflow_amd.builders.NSMarkovBuilder",
     "fourierflow.builders.NSZongyiBuilder": "fourierflow_amd.builders.NSZongyiBuilder",
+    "fourierflow.builders.NSContextualBuilder": "fourierflow_amd.builders.NSContextualBuilder",
 }
 _INTERP = re.compile(r"^\$\{\s*([\w.]+)\s*:\s*(.*?)\s*\}$")
 

@@ -714,6 +714,8 @@ __global__ __launch_bounds__(256) void markov_traj_metrics_kernel(const float* _
 // One launch per batch: block (slice, sample) looks up its sample's pair id and walks the pixels of its slice, reading t - k, t
 // and t + k from the pixel's own T-row of the time-last set (4-byte accesses T floats apart, as in the trajectory step above) and
 // writing the pixel-major outputs coalesced.  An id outside [0, total) reads nothing of the set and fills its sample with NaN.
+// The force is one map per trajectory (Tf = 0: a coalesced row of f) or one per snapshot (Tf > 0: f is time-last like the set,
+// and the pixel reads entry t + k of its own Tf-row, the same strided 4-byte access as the three above).
 struct MarkovPairs {
     const float* data;
     const int32_t* ids;
@@ -723,6 +725,7 @@ struct MarkovPairs {
     const float* mu;
     float* mu_out;
     int n, T, t0, k, P, total;      // n = M N pixels per field; total = trajectories x P
+    int Tf;                         // force maps per trajectory along f's last axis, or 0: one map [n]
 };
 
 __global__ __launch_bounds__(256) void markov_pairs_kernel(MarkovPairs a) {
@@ -742,7 +745,7 @@ __global__ __launch_bounds__(256) void markov_pairs_kernel(MarkovPairs a) {
             xv = row[t];
             if (a.y || a.dy) yv = row[t + a.k];
             if (a.dx) pv = row[t - a.k];
-            if (a.f_out) fv = a.f[src + e];
+            if (a.f_out) fv = a.Tf ? a.f[(src + e) * a.Tf + t + a.k] : a.f[src + e];
         }
         if (a.x) a.x[dst + e] = xv;
         if (a.y) a.y[dst + e] = yv;
@@ -1189,17 +1192,24 @@ extern "C" int ffno_markov_advance(const float* out, float* field, const ffno_ma
 }
 
 // (one pixel per thread up to 64 slices of a field: a launch of many short, latency-bound row reads wants its workgroups wide)
-extern "C" int ffno_markov_pairs(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f,
-                                 float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k, int P,
-                                 int B, void* stream) {
+extern "C" int ffno_markov_pairs_tf(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f,
+                                    int Tf, float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k,
+                                    int P, int B, void* stream) {
     if (!data || !ids || (!x && !y && !dx && !dy) || n <= 0 || M <= 0 || N <= 0 || T <= 0 || k <= 0 || P <= 0 || B <= 0 || t0 < 0)
         return FFNO_EINVAL;
     if ((long)t0 + P - 1 + k > (long)T - 1 || (dx && t0 < k) || (f_out && !f) || (mu_out && !mu)) return FFNO_EINVAL;
+    if (Tf < 0 || (Tf > 0 && (long)t0 + P - 1 + k > (long)Tf - 1)) return FFNO_EINVAL;
     if ((long)M * N > 0x7fffffffL || (long)n * P > 0x7fffffffL || B > 65535) return FFNO_EUNSUPPORTED;
     const int px = M * N;
-    MarkovPairs a{data, ids, x, y, dx, dy, f, f_out, mu, mu_out, px, T, t0, k, P, n * P};
+    MarkovPairs a{data, ids, x, y, dx, dy, f, f_out, mu, mu_out, px, T, t0, k, P, n * P, Tf};
     FFNO_LAUNCH(markov_pairs_kernel, dim3(max(1, min(64, (px + 255) / 256)), B), dim3(256), 0, (hipStream_t)stream, a);
     return pw_status();
+}
+
+extern "C" int ffno_markov_pairs(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f,
+                                 float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k, int P,
+                                 int B, void* stream) {
+    return ffno_markov_pairs_tf(data, ids, x, y, dx, dy, f, 0, f_out, mu, mu_out, n, M, N, T, t0, k, P, B, stream);
 }
 
 // (up to 64 slices of 256 lanes per sample and field, sized by the launch's largest field; a slice of a smaller field that

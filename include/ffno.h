@@ -80,7 +80,7 @@ const char* ffno_build_target(void);
  * library under newer host code would have read shifted arguments).  ffno_abi_version() returns the value the LIBRARY was built
  * with; a caller compares it with the FFNO_ABI_VERSION it was compiled against before the first compute call (the Python host
  * does: fourierflow_amd/_lib.py refuses a mismatch). */
-#define FFNO_ABI_VERSION 7
+#define FFNO_ABI_VERSION 8
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -934,6 +934,16 @@ int ffno_markov_advance(const float* out, float* field, const ffno_markov_advanc
 int ffno_markov_pairs(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f,
                       float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k, int P, int B,
                       void* stream);
+/* The same with a force map per time step -- the pairs of the contextual NavierStokesTrainingDataset
+ * (builders/ns_contextual.py:45-72: `constant_force = len(f.shape) == 3` :52, the two branches :63-66), which is t0 = 0, k,
+ * P = T - k without dx / dy:
+ *   Tf > 0:  f [n][M][N][Tf] is time-last like data, and  f_out[i][m][n] = f[b][m][n][t + k]  -- the force at the TARGET time (:66)
+ *   Tf == 0: f [n][M][N]; the call is ffno_markov_pairs, bit for bit (that entry forwards here: one kernel serves both)
+ * FFNO_EINVAL: the cases above, Tf < 0, and Tf > 0 with t0 + P - 1 + k > Tf - 1 (the last pair's force would lie past f's rows).
+ * An id outside [0, n P) fills f_out of that sample with NaN like the other outputs. */
+int ffno_markov_pairs_tf(const float* data, const int32_t* ids, float* x, float* y, float* dx, float* dy, const float* f, int Tf,
+                         float* f_out, const float* mu, float* mu_out, int n, int M, int N, int T, int t0, int k, int P, int B,
+                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * A training / validation batch drawn from sample sets on the device, every field of it in one launch: what indexing the
