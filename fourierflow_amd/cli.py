@@ -7,6 +7,8 @@ commands/predict.py:24-110, commands/infer.py) for the routines built here, with
 
     <config_dir>/checkpoints/trial-<trial>-<id>/epoch=<e>-step=<s>-valid_loss=<v>.ckpt   (best, what `test` / `predict` load)
     <config_dir>/checkpoints/trial-<trial>-<id>/last.ckpt                                 (what `--resume` continues from)
+    (KolmogorovBuilder configs under `--builder`: the best file is chosen and named by the config's CustomModelCheckpoint entry,
+     epoch=<e>-step=<s>-valid_time_until=<v>.ckpt for the torus_kochkov configs)
 
 What is NOT here is the reference's control plane: Hydra (the loader of fourierflow_amd/config.py resolves the same
 interpolations), Lightning (the routines run their own fused step), wandb (one JSON line per logged step on stdout)
@@ -21,12 +23,15 @@ configured geometry (point clouds: ``xy`` uniform in [0, 1)^2, 972 points unless
 
 ``train CONFIG --builder`` and ``test CONFIG --builder`` run the routines the way the reference does: on the dataset files of the
 config's ``builder`` section (StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder: builders/mesh_data.py; NSMarkovBuilder,
-NSZongyiBuilder: builders/ns_data.py; NSContextualBuilder: builders/ns_contextual.py), split by ``train_size`` / ``valid_size`` /
-``test_size`` (NSContextualBuilder: by its train / valid / test files), in shuffled epochs drawn on the
+NSZongyiBuilder: builders/ns_data.py; NSContextualBuilder: builders/ns_contextual.py; KolmogorovBuilder: builders/kolmogorov.py),
+split by ``train_size`` / ``valid_size`` / ``test_size`` (NSContextualBuilder: by its train / valid / test files; KolmogorovBuilder: by
+the files of its three dataset nodes, each ``P.nc`` read from ``P.npz`` beside it), in shuffled epochs drawn on the
 device, with the validation split evaluated after every epoch and the best checkpoint kept.  For the Markov routine epoch 0 is
 the reference's statistics epoch: one whole pass that only accumulates the normaliser.  ``predict CONFIG --builder`` runs on the
 builder's ``inference_data()`` and reports the reference's ``inference_time``; NSContextualBuilder has none, in the reference
-either, and is refused there.
+either, and is refused there.  With KolmogorovBuilder the routine reduces its predictions to the grid of ``corr_data`` on the device
+(``downsample_corr``), ``valid_corr`` / ``valid_reduced_time_until`` are the reduced ones, the checkpoint is selected by the config's
+``CustomModelCheckpoint`` entry (``valid_time_until``, max) and `test --builder` also prints ``test_reduced_time_until``.
 """
 from __future__ import annotations
 
@@ -177,13 +182,14 @@ def _trajectory_batches(routine, cfg, dev, path: Path, batch_size: Optional[int]
 
 # the classes `--builder` runs and the routine each one feeds
 BUILDERS = {"StructuredMesh2DBuilder": "mesh", "PlasticityBuilder": "mesh", "ElasticityBuilder": "pointcloud",
-            "NSMarkovBuilder": "markov", "NSZongyiBuilder": "rollout", "NSContextualBuilder": "markov"}
+            "NSMarkovBuilder": "markov", "NSZongyiBuilder": "rollout", "NSContextualBuilder": "markov",
+            "KolmogorovBuilder": "markov"}
 _ROUTINES = {"mesh": "StructuredMeshExperiment", "pointcloud": "PointCloudExperiment", "markov": "Grid2DMarkovExperiment",
              "rollout": "Grid2DRolloutExperiment"}
 
 
 def _instantiate_builder(cfg, kind: str, batch_size: Optional[int], routine=None):
-    """The config's `builder` section as one of builders/mesh_data.py / ns_data.py / ns_contextual.py (`${oc.env:DATA_ROOT}` resolved like everywhere
+    """The config's `builder` section as one of builders/mesh_data.py / ns_data.py / ns_contextual.py / kolmogorov.py (`${oc.env:DATA_ROOT}` resolved like everywhere
     else).  A section that names another builder than the routine's, none at all, or lacks an argument its class requires is
     refused before anything is read."""
     import inspect
@@ -206,6 +212,8 @@ def _instantiate_builder(cfg, kind: str, batch_size: Optional[int], routine=None
     bld = instantiate(node)
     if routine is not None and hasattr(bld, "append_force"):      # f / mu go along when the routine appends them
         bld.append_force, bld.append_mu = bool(routine.append_force), bool(routine.append_mu)
+    if name == "KolmogorovBuilder" and routine is not None:      # its corr_data lives on a coarser grid than the model (32 x 32)
+        routine.downsample_corr = True
     if kind == "rollout" and routine is not None and \
             (bld.n_steps != routine.n_steps or bld.append_pos != bool(routine.append_pos)):
         raise ValueError(f"builder n_steps = {bld.n_steps}, append_pos = {bld.append_pos} but the routine rolls out n_steps = "
@@ -241,6 +249,26 @@ TEST_KEYS = {"markov": ("test_loss", "test_loss_avg", "test_time_until", "test_c
              "rollout": ("test_loss", "test_loss_avg", "test_time_until")}
 
 
+def _checkpoint_rule(cfg, bld):
+    """(monitor, mode, file name template) of the best checkpoint.  Every builder but KolmogorovBuilder: valid_loss / min and the
+    name epoch=<e>-step=<s>-valid_loss=<v>.ckpt (template None).  KolmogorovBuilder: the config's CustomModelCheckpoint entry
+    (torus_kochkov: monitor valid_time_until, mode max, filename "{epoch}-{step}-{valid_time_until:.3f}"), the name written the way
+    Lightning writes it: every `{key` of the template becomes `key={key`."""
+    if type(bld).__name__ != "KolmogorovBuilder":
+        return "valid_loss", "min", None
+    entry = next((c for c in (cfg.get("callbacks") or []) if isinstance(c, dict) and
+                  str(c.get("_target_", "")).endswith("CustomModelCheckpoint")), {})
+    monitor, mode = str(entry.get("monitor", "valid_loss")), str(entry.get("mode", "min"))
+    if mode not in ("min", "max"):
+        raise ValueError(f"CustomModelCheckpoint.mode is min or max, got {mode!r}")
+    return monitor, mode, str(entry.get("filename") or "{epoch}-{step}-{%s:.5f}" % monitor)
+
+
+def _checkpoint_name(template: str, **values) -> str:
+    import re
+    return re.sub(r"\{([A-Za-z_]\w*)", r"\1={\1", template).format(**values) + ".ckpt"
+
+
 def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial, checkpoint_id, no_logging, force, resume, epochs,
                         no_shuffle, drop_last, batch_size):
     """`train --builder`: whole epochs over the builder's training split, validation over its whole validation split after every
@@ -248,6 +276,8 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
     Markov routine with `should_normalize` spends epoch 0 on the normaliser statistics alone (grid_2d_markov.py:374-390): no
     optimisation step is taken, `global_step` stands still, and the epoch is validated and checkpointed like any other."""
     bld = _instantiate_builder(cfg, kind, batch_size, routine)
+    monitor, mode, template = _checkpoint_rule(cfg, bld)
+    worst = math.inf if mode == "min" else -math.inf
     n_epochs = epochs or int((cfg.get("trainer") or {}).get("max_epochs", 0))
     if n_epochs < 1:
         raise ValueError("--builder runs whole epochs: pass --epochs E or set trainer.max_epochs in the config")
@@ -258,14 +288,14 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
     if out_dir is not None and force and not resume:
         for old in out_dir.glob("*.ckpt"):
             old.unlink()
-    start, best = dict(epoch=0, global_step=0), math.inf
+    start, best = dict(epoch=0, global_step=0), worst
     if resume:
         if trial_dir is None or not (trial_dir / "last.ckpt").exists():
             raise FileNotFoundError("--resume needs checkpoints/trial-<trial>-*/last.ckpt (commands/train.py:74-80)")
         start = routine.resume_from_checkpoint(str(trial_dir / "last.ckpt"))
         # the best validation loss so far: last.ckpt carries it, as Lightning's carries its checkpoint callback's state
         saved = torch.load(str(trial_dir / "last.ckpt"), map_location="cpu", weights_only=False).get("callbacks") or {}
-        best = float((saved.get("ModelCheckpoint") or {}).get("best_model_score", math.inf))
+        best = float((saved.get("ModelCheckpoint") or {}).get("best_model_score", worst))
         for _ in range(start["epoch"] if train_set.shuffle else 0):      # the permutations of the epochs already run
             train_set._epoch_ids()
     if hasattr(routine, "current_epoch"):
@@ -291,18 +321,22 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
         if hasattr(routine, "on_train_epoch_end"):
             routine.on_train_epoch_end()
         valid = _split_loss(routine, valid_set)
+        if monitor not in valid:
+            raise KeyError(f"the checkpoint monitor {monitor!r} is not among the validation keys {sorted(valid)}")
+        score = valid[monitor]
         vl = valid.pop("valid_loss")
-        improved = vl < best
+        improved = score < best if mode == "min" else score > best      # strictly better, or the earlier file stays
         if out_dir is not None:
             if improved:
                 for old in out_dir.glob("epoch*.ckpt"):
                     old.unlink()
-                routine.save_checkpoint(str(out_dir / f"epoch={epoch + 1}-step={gs}-valid_loss={vl:.5f}.ckpt"), epoch=epoch + 1,
-                                        global_step=gs)
-        best = min(best, vl)
+                name = f"epoch={epoch + 1}-step={gs}-valid_loss={vl:.5f}.ckpt" if template is None else \
+                    _checkpoint_name(template, epoch=epoch + 1, step=gs, valid_loss=vl, **valid)
+                routine.save_checkpoint(str(out_dir / name), epoch=epoch + 1, global_step=gs)
+        best = score if improved else best
         if out_dir is not None:
             last = routine.checkpoint_dict(epoch + 1, gs)
-            last["callbacks"] = {"ModelCheckpoint": dict(monitor="valid_loss", best_model_score=best)}
+            last["callbacks"] = {"ModelCheckpoint": dict(monitor=monitor, best_model_score=best)}
             torch.save(last, str(out_dir / "last.ckpt"))
         if rank == 0:
             print(json.dumps(dict(epoch=epoch + 1, step=gs, train_loss=None if lv is None else round(lv, 6), lr=lr,
@@ -315,7 +349,7 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
     if rank == 0:
         print(json.dumps(dict(steps=steps, batch=train_set.batch_size, world_size=world, epochs=n_epochs - start["epoch"],
                               steps_per_s=round(steps / max(dt, 1e-9), 2), resumed_from_step=start["global_step"],
-                              **({} if best == math.inf else dict(valid_loss=round(best, 6))))), flush=True)
+                              **({} if best == worst else {monitor: round(best, 6)}))), flush=True)
     if world > 1:
         torch.distributed.barrier()
 
@@ -396,7 +430,7 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
                                                        "default) or kolmogorov (inputs 0 ... T-1-k)"),
           builder: bool = Option(False, "--builder", help="train on the dataset files of the config's `builder` section "
                                                           "(StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder, "
-                                                          "NSMarkovBuilder, NSZongyiBuilder, NSContextualBuilder) for --epochs (default "
+                                                          "NSMarkovBuilder, NSZongyiBuilder, NSContextualBuilder, KolmogorovBuilder) for --epochs (default "
                                                           "trainer.max_epochs) whole epochs, validating on the held-out split after "
                                                           "each; the Markov routine's epoch 0 only accumulates its normaliser"),
           device: Optional[str] = Option(None, hidden=True)):
@@ -516,7 +550,8 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
          batches: int = Option(1, help="test batches to average over"), data: Optional[Path] = None,
          batch_size: Optional[int] = None, grid: int = 64, size: Optional[List[int]] = None,
          builder: bool = Option(False, "--builder", help="the test metrics over the whole test split of the config's `builder` "
-                                                         "section"),
+                                                         "section (KolmogorovBuilder: with test_reduced_time_until, on the grid "
+                                                         "of its corr_data)"),
          device: Optional[str] = Option(None, hidden=True)):
     """Test: load the best checkpoint of the trial (or `checkpoint_path=...` override) and report the test metrics."""
     if builder and data is not None:
@@ -530,9 +565,11 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
     routine.to(dev)
     routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
     if builder:
-        test_set = _instantiate_builder(cfg, kind, batch_size, routine).test_data(dev)
+        bld = _instantiate_builder(cfg, kind, batch_size, routine)
+        test_set = bld.test_data(dev)
         if kind in TEST_KEYS:
-            m = _split_loss(routine, test_set, "test_step", TEST_KEYS[kind])
+            reduced = ("test_reduced_time_until",) if type(bld).__name__ == "KolmogorovBuilder" else ()
+            m = _split_loss(routine, test_set, "test_step", TEST_KEYS[kind] + reduced)
         else:
             m = dict(test_loss=_split_loss(routine, test_set)["valid_loss"])
         print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in m.items()}, samples=test_set.n)), flush=True)
@@ -563,7 +600,8 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
             batch_size: Optional[int] = Option(None, help="default 1; with --builder: trajectories per chunk, default all at once"),
             grid: int = 64, size: Optional[List[int]] = None,
             builder: bool = Option(False, "--builder", help="Markov and rollout routines: predict on the `inference_data()` of the "
-                                                            "config's `builder` section (the first 512 trajectories of its file) "
+                                                            "config's `builder` section (the first 512 trajectories of its file; "
+                                                            "KolmogorovBuilder: its test trajectories) "
                                                             "and report the reference's `inference_time`"),
             device: Optional[str] = Option(None, hidden=True)):
     """Predict: load the best checkpoint, run the model autoregressively (grid routines) or once (mesh routine), save the
@@ -581,7 +619,7 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     traj = None
     if builder:
         if kind not in TEST_KEYS:
-            raise ValueError("predict --builder runs the Markov and rollout routines (NSMarkovBuilder, NSZongyiBuilder), whose "
+            raise ValueError("predict --builder runs the Markov and rollout routines (NSMarkovBuilder, NSZongyiBuilder, KolmogorovBuilder), whose "
                              "builders have inference_data()")
         bld = _instantiate_builder(cfg, kind, None, routine)
         if not hasattr(bld, "inference_data"):

@@ -7,7 +7,8 @@ drives the hot path -- ``routine`` with its ``conv`` / ``model``, ``optimizer`` 
 maps ``fourierflow.*`` targets onto their MI355X-native mirrors, so an unmodified torus_li config builds
 the HIP-backed routine.  ``build_routine`` leaves the other sections alone; of them the CLI's ``--builder`` instantiates a
 ``builder`` section that names StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder (builders/mesh_data.py),
-NSMarkovBuilder, NSZongyiBuilder (builders/ns_data.py) or NSContextualBuilder (builders/ns_contextual.py) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
+NSMarkovBuilder, NSZongyiBuilder (builders/ns_data.py), NSContextualBuilder (builders/ns_contextual.py) or KolmogorovBuilder with its
+KolmogorovTorchDataset / KolmogorovTrajectoryDataset nodes (builders/kolmogorov.py) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
 scope).
 """
 from __future__ import annotations
@@ -44,6 +45,13 @@ TARGET_MAP = {
     "fourierflow.builders.NSMarkovBuilder": "fourierflow_amd.builders.NSMarkovBuilder",
     "fourierflow.builders.NSZongyiBuilder": "fourierflow_amd.builders.NSZongyiBuilder",
     "fourierflow.builders.NSContextualBuilder": "fourierflow_amd.builders.NSContextualBuilder",
+    "fourierflow.builders.KolmogorovBuilder": "fourierflow_amd.builders.KolmogorovBuilder",
+    "fourierflow.builders.KolmogorovTorchDataset": "fourierflow_amd.builders.KolmogorovTorchDataset",
+    "fourierflow.builders.KolmogorovTrajectoryDataset": "fourierflow_amd.builders.KolmogorovTrajectoryDataset",
+    # (these three raise a NotImplementedError that names them and says what they would need)
+    "fourierflow.builders.KolmogorovMultiTorchDataset": "fourierflow_amd.builders.KolmogorovMultiTorchDataset",
+    "fourierflow.builders.KolmogorovJAXDataset": "fourierflow_amd.builders.KolmogorovJAXDataset",
+    "fourierflow.builders.KolmogorovJAXTrajectoryDataset": "fourierflow_amd.builders.KolmogorovJAXTrajectoryDataset",
 }
 _INTERP = re.compile(r"^\$\{\s*([\w.]+)\s*:\s*(.*?)\s*\}$")
 
@@ -145,6 +153,9 @@ def instantiate(node: Any) -> Any:
 def build_routine(cfg: Dict[str, Any]):
     """Instantiate ``cfg['routine']`` (the model + optimiser + schedule); other sections are left alone."""
     r = dict(cfg["routine"])
+    if str(r.get("_target_", "")).endswith(".LearnedInterpolator"):      # before its optax / jax-cfd nodes are looked at
+        raise NotImplementedError(f"{r['_target_']} (the learned-interpolation baseline of jax-cfd) has no MI355X-native "
+                                  f"counterpart in fourierflow_amd (see DESIGN.md section 7)")
     opt = instantiate(r.pop("optimizer", None)) if r.get("optimizer") else None
     sch = instantiate(r.pop("scheduler", None)) if r.get("scheduler") else None
     r.pop("optimizer", None)

@@ -171,3 +171,7 @@ extern "C" int ffno_velocity_features(const float* vorticity, float* out, float*
                 vorticity, Zq, Zv, out, X, Y, Yh);
     return vel_status();
 }
+
+// the reduction of a velocity image to the grid of corr_data and its correlation sums (entry points ffno_vorticity_coarsen_*,
+// ffno_markov_corr_metrics): what the validation of the torus_kochkov configs runs on the output of the launch above
+#include "ffno_coarsen.h"

@@ -3,7 +3,8 @@
 without Lightning / wandb / jax: feature build (positional channels, running normaliser, Gaussian noise),
 the operator, inverse-normalise + relative-L2 loss, the manual optimisation step
 (routines/base.py:27-52), epoch-0 statistics accumulation, the autoregressive rollout used by predict/infer, and the
-trajectory validation / test metrics of ``_valid_step`` / ``compute_losses`` / ``validation_step`` / ``test_step`` (:195-416).
+trajectory validation / test metrics of ``_valid_step`` / ``compute_losses`` / ``validation_step`` / ``test_step`` (:195-416),
+with ``downsample_corr=True`` including the correlation on the reduced grid of ``corr_data`` (:350-370, utils/array.py:18-80).
 
 Everything on the device is a HIP kernel of libffno_hip.so; torch supplies memory, the stream and the
 Gaussian noise samples.
@@ -31,7 +32,8 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                  max_accumulations: float = 1e6, should_normalize: bool = True, use_fourier_position: bool = False,
                  noise_std: float = 0.0, shuffle_grid: bool = False, use_velocity: bool = False,
                  learn_difference: bool = False, step_size: float = 1.0, optimizer: Optional[dict] = None,
-                 scheduler: Optional[dict] = None, domain=((0.0, 2 * math.pi), (0.0, 2 * math.pi)), grid_size=(64,), **unused):
+                 scheduler: Optional[dict] = None, domain=((0.0, 2 * math.pi), (0.0, 2 * math.pi)), grid_size=(64,),
+                 downsample_corr: bool = False, **unused):
         super().__init__()
         reject_unsupported_routine_kwargs(unused)
         if use_fourier_position:
@@ -64,6 +66,9 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                 self.register_buffer(f'ky_{size}', torch.from_numpy(ky.astype(np.float32)))
                 self.register_buffer(f'lap_{size}', torch.from_numpy(lap.astype(np.complex64)))
         self._vel_ws = None
+        # corr_data of another grid size than the model's: reduce every prediction to it on the device (ffno_vorticity_coarsen_step)
+        # where the reference calls downsample_vorticity; off, such a batch is refused as before
+        self.downsample_corr = bool(downsample_corr)
         self._opt_kw = dict(lr=2.5e-3, weight_decay=1e-4)
         self._opt_kw.update(optimizer or {})
         # the F-FNO configs run cosine-with-warm-up per step; the FNOZongyi2DBlock ablations (torus_li/ablation/zongyi_markov*)
@@ -97,7 +102,8 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         x = batch['x'].contiguous()
         _lib.require_device_tensor(x, "batch['x']")
         if self.use_velocity:       # [B, M, N, 1] vorticity -> [B, M, N, 3] (vorticity, u, v)  (grid_2d_markov.py:130-144)
-            x = self._velocity(x)
+            vel = batch.get('velocity')      # the same launch's output for this very x, where the caller holds it already
+            x = self._velocity(x) if vel is None else vel
         B, M, N, Cx = x.shape
         extra, keep = None, []
         if not self.use_position or self.append_force or self.append_mu:      # grid_2d_markov.py:146-162
@@ -341,7 +347,9 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                 raise ValueError(f"batch['f'] holds {force.shape[-1]} force maps, the rollout needs {n_steps}")
         mu = batch['mu'] if self.append_mu else None
         sums = torch.empty(int(lib.ffno_markov_traj_ws_floats(B, M, N, n_steps)), dtype=torch.float32, device=dev)
-        metrics = torch.empty(4 + 2 * n_steps, dtype=torch.float32, device=dev)
+        corr = self._reduced_corr(batch, B, M, N, n_steps)      # None: corr_data absent, of the grid's own size, or the switch off
+        metrics = torch.empty(4 + 2 * n_steps + (2 + n_steps if corr is not None else 0), dtype=torch.float32, device=dev)
+        sums2 = self._coarsen_sums(corr, B, n_steps)
         preds = torch.empty(B, M, N, n_steps, dtype=torch.float32, device=dev)
         im = data[..., T - n_steps - 1].unsqueeze(-1).contiguous()      # the first input; then every prediction, in place
         prev = _p(im) if self.learn_difference else None                 # prev_im is the running field itself (:316-318)
@@ -349,10 +357,10 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         was_training = self.normalizer.training
         self.normalizer.eval()
         try:
-            affine = None
+            affine = vel = None
             for t in range(n_steps):
                 f_t = force if force is None or force.dim() == 3 else force[..., t].contiguous()
-                feats = self._build_features({'x': im, 'f': f_t, 'mu': mu}, add_noise=False)
+                feats = self._build_features({'x': im, 'f': f_t, 'mu': mu, 'velocity': vel}, add_noise=False)
                 if t == 0:      # the statistics stand still during validation: one inverse affine for the whole rollout
                     affine = self._affine_tensor()
                 out = self._unshuffle(tr.engine.forward(self._shuffle(feats), False))
@@ -360,10 +368,17 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                     raise ValueError(f"the rollout feeds one predicted channel back, conv returned {tuple(out.shape)}")
                 _capi.check(lib.ffno_markov_traj_step(_p(out), _p(affine), prev, _p(data), _p(im), _p(preds), _p(sums),
                                                       B, M, N, T, n_steps, t, stream), "markov_traj_step")
+                if corr is not None:      # the velocity image of this prediction: reduced here, and the next step's features
+                    vel = self._velocity(im)
+                    self._coarsen_step(vel, corr, sums2, n_steps, t)
+                    if not self.use_velocity:
+                        vel = None
         finally:
             self.normalizer.train(was_training)
         _capi.check(lib.ffno_markov_traj_metrics(_p(sums), _p(metrics), B, M, N, n_steps, 0.95, stream), "markov_traj_metrics")
-        self._traj = (preds, metrics)
+        if corr is not None:
+            self._corr_metrics(sums2, metrics, corr, B, n_steps)
+        self._traj = (preds, metrics, corr is not None)
         step_losses = metrics[4:4 + n_steps]
         return step_losses.sum(), step_losses, preds, []
 
@@ -374,11 +389,14 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         (their sums 2..5 depend on the predictions alone).  One host read: `self.last_metrics`."""
         data = batch['data'].contiguous().float()
         B, M, N, T, n_steps = self._traj_geometry(data)
-        if 'corr_data' in batch and batch['corr_data'].shape[1] != M:
+        if 'corr_data' in batch and batch['corr_data'].shape[1] != M and not self.downsample_corr:
             raise NotImplementedError("corr_data of another grid size needs downsample_vorticity (jax-cfd), which is not built: "
-                                      "pass corr_data at the model's own resolution")
+                                      "pass corr_data at the model's own resolution, or build the routine with downsample_corr=True "
+                                      "to reduce the predictions on the device (ffno_vorticity_coarsen_step)")
+        corr = self._reduced_corr(batch, B, M, N, n_steps)
+        base = 4 + 2 * n_steps      # where the reduced numbers { diverged_t, mean_t p_2, p_2[n_steps] } follow the full ones
         cached = getattr(self, "_traj", None)
-        if cached is not None and cached[0] is preds:
+        if cached is not None and cached[0] is preds and cached[2] == (corr is not None):
             metrics = cached[1]
             loss = metrics[0]
         else:
@@ -387,20 +405,71 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
             _lib.require_device_tensor(preds, "preds")
             lib, stream = _lib.get_lib(), _lib.current_stream(data.device)
             sums = torch.empty(int(lib.ffno_markov_traj_ws_floats(B, M, N, n_steps)), dtype=torch.float32, device=data.device)
-            metrics = torch.empty(4 + 2 * n_steps, dtype=torch.float32, device=data.device)
+            metrics = torch.empty(base + (2 + n_steps if corr is not None else 0), dtype=torch.float32, device=data.device)
+            sums2 = self._coarsen_sums(corr, B, n_steps)
             im, again = torch.empty(B, M, N, dtype=torch.float32, device=data.device), torch.empty_like(preds)
             for t in range(n_steps):
                 col = preds[..., t].contiguous().float()
                 _capi.check(lib.ffno_markov_traj_step(_p(col), None, None, _p(data), _p(im), _p(again), _p(sums),
                                                       B, M, N, T, n_steps, t, stream), "markov_traj_step")
+                if corr is not None:
+                    self._coarsen_step(self._velocity(col.unsqueeze(-1)), corr, sums2, n_steps, t)
             _capi.check(lib.ffno_markov_traj_metrics(_p(sums), _p(metrics), B, M, N, n_steps, 0.95, stream), "markov_traj_metrics")
+            if corr is not None:
+                self._corr_metrics(sums2, metrics, corr, B, n_steps)
             loss = loss / n_steps
         host = metrics.cpu()
         self.last_metrics = host
         time_until = float(host[2]) * self.step_size
         times = batch['times'][0, -n_steps:] if 'times' in batch else None
+        if corr is not None:      # p is p_2, and the logged mean correlation with it; time_until stays the full one (:358-372)
+            self.last_corr = float(host[base + 1])
+            return loss, metrics[1], time_until, float(host[base]) * self.step_size, metrics[base + 2:], times
         # corr_data at the grid's own size: the reduced metrics ARE the full ones (:351-357)
-        return loss, metrics[1], time_until, time_until, metrics[4 + n_steps:], times
+        self.last_corr = float(host[3])
+        return loss, metrics[1], time_until, time_until, metrics[4 + n_steps:base], times
+
+    # -- the correlation on the grid of corr_data (:350-370) -------------------------------------------------------------------
+    def _reduced_corr(self, batch, B: int, M: int, N: int, n_steps: int) -> Optional[torch.Tensor]:
+        """batch['corr_data'] [B, m, m, Tc] where the predictions have to be reduced to its grid, else None."""
+        if not self.downsample_corr or 'corr_data' not in batch or batch['corr_data'].shape[1] == M:
+            return None
+        corr = batch['corr_data']
+        _lib.require_device_tensor(corr, "batch['corr_data']")
+        shape = tuple(corr.shape)
+        if corr.dim() != 4 or shape[0] != B:
+            raise ValueError(f"batch['corr_data'] must be [{B}, m, m, Tc], got {shape}")
+        if shape[1] != shape[2]:
+            raise ValueError(f"batch['corr_data'] {shape} is not square: the reduction of a {M} x {N} prediction takes one factor "
+                             f"for both directions")
+        m = shape[1]
+        if M % m or N % m or M // m != N // m:
+            raise ValueError(f"batch['corr_data'] {shape}: a {M} x {N} prediction is reduced by an integer factor, the same in both "
+                             f"directions, and {M} / {m}, {N} / {m} is none")
+        if shape[3] < n_steps:
+            raise ValueError(f"batch['corr_data'] {shape} holds {shape[3]} steps, the rollout of batch['data'] "
+                             f"{tuple(batch['data'].shape)} compares {n_steps}")
+        return corr.contiguous().float()
+
+    def _coarsen_sums(self, corr, B: int, n_steps: int) -> Optional[torch.Tensor]:
+        if corr is None:
+            return None
+        n = int(_lib.get_lib().ffno_vorticity_coarsen_ws_floats(B, corr.shape[1], n_steps))
+        if n == 0:
+            raise ValueError(f"batch['corr_data'] {tuple(corr.shape)}: grid size outside ffno_vorticity_coarsen_step's range")
+        return torch.empty(n, dtype=torch.float32, device=corr.device)
+
+    def _coarsen_step(self, vel: torch.Tensor, corr: torch.Tensor, sums2: torch.Tensor, n_steps: int, t: int):
+        B, M, N, _ = vel.shape
+        lx, ly = self.domain[0][1] - self.domain[0][0], self.domain[1][1] - self.domain[1][0]
+        _capi.check(_lib.get_lib().ffno_vorticity_coarsen_step(_p(vel), _p(corr), None, _p(sums2), B, M, N, corr.shape[1],
+                                                               corr.shape[3], n_steps, t, lx, ly,
+                                                               _lib.current_stream(vel.device)), "vorticity_coarsen_step")
+
+    def _corr_metrics(self, sums2: torch.Tensor, metrics: torch.Tensor, corr: torch.Tensor, B: int, n_steps: int):
+        tail = ctypes.c_void_p(metrics.data_ptr() + 4 * (4 + 2 * n_steps))
+        _capi.check(_lib.get_lib().ffno_markov_corr_metrics(_p(sums2), tail, B, corr.shape[1], n_steps, 0.95,
+                                                            _lib.current_stream(metrics.device)), "markov_corr_metrics")
 
     def _trajectory_metrics(self, batch):
         loss, step_losses, preds, _ = self._valid_step(batch)
@@ -417,14 +486,14 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         if math.isnan(float(host[1])):
             loss_full = 9999.9
         return {'valid_loss_avg': loss, 'valid_loss': loss_full, 'valid_time_until': time_until,
-                'valid_reduced_time_until': reduced, 'valid_corr': float(host[3])}
+                'valid_reduced_time_until': reduced, 'valid_corr': self.last_corr}
 
     def test_step(self, batch, batch_idx: int = 0):
         """The reference's logged test keys (:408-425); its two wandb tables are returned as `test_correlations` (p per step)
         and `test_losses` (relative-L2 per step), with `test_times` when the batch carries `times`."""
         loss, loss_full, time_until, reduced, p, times, step_losses = self._trajectory_metrics(batch)
         out = {'test_loss_avg': loss, 'test_loss': loss_full, 'test_time_until': time_until,
-               'test_reduced_time_until': reduced, 'test_corr': float(self.last_metrics[3]),
+               'test_reduced_time_until': reduced, 'test_corr': self.last_corr,
                'test_correlations': p, 'test_losses': step_losses}
         if times is not None:
             out['test_times'] = times

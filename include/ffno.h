@@ -79,8 +79,9 @@ const char* ffno_build_target(void);
  * ffno_fused_branch, the layer descriptors and inserted range-word arguments before `stream` without bumping it: an older
  * library under newer host code would have read shifted arguments).  ffno_abi_version() returns the value the LIBRARY was built
  * with; a caller compares it with the FFNO_ABI_VERSION it was compiled against before the first compute call (the Python host
- * does: fourierflow_amd/_lib.py refuses a mismatch). */
-#define FFNO_ABI_VERSION 8
+ * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
+ * binds at load -- a library of generation 8 lacks them. */
+#define FFNO_ABI_VERSION 9
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -880,6 +881,32 @@ int ffno_markov_traj_step(const float* out, const float* affine, const float* pr
                           float* preds, float* sums, int B, int M, int N, int T, int n_steps, int t, void* stream);
 int ffno_markov_traj_metrics(const float* sums, float* metrics, int B, int M, int N, int n_steps, float threshold,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Reduced-grid correlation of the Markov routine's validation (utils/array.py:18-80 downsample_vorticity, called at
+ * routines/grid_2d_markov.py:353-370): a prediction's vorticity on the m x m grid of `corr_data` and its correlation with it.
+ * fp32, deterministic (fixed slices added in a fixed order, no atomics), every output written exactly once.
+ *
+ * ffno_vorticity_coarsen_step -- one launch per rollout step t.  vel [B][X][Y][3] is the output of ffno_velocity_features for the
+ * de-normalised prediction (channels 1, 2 = u, v); f = X / m = Y / m is an integer, dx = len_x / m, dy = len_y / m:
+ *   u_c[i][j] = (sum_{b<f} u[f i + f-1][f j + b]) / f      v_c[i][j] = (sum_{a<f} v[f i + a][f j + f-1]) / f     (index order)
+ *   w_c[i][j] = (v_c[(i+1) % m][j] - v_c[i][j]) / dx - (u_c[i][(j+1) % m] - u_c[i][j]) / dy
+ *   preds2[b][i][j][t] = w_c                                   (preds2 [B][m][m][n_steps]; NULL = not stored)
+ *   sums[t][b][slice][0..2] = partial sums over the slice's coarse rows of  w_c^2, c^2, w_c c,  c = corr[b][i][j][Tc - n_steps + t]
+ *   (corr [B][m][m][Tc]).  sums holds ffno_vorticity_coarsen_ws_floats(B, m, n_steps) = n_steps B S 3 floats, S slices of
+ *   ceil(m / S') rows with S' = min(m, ceil(m m / 1024)).
+ *   FFNO_EINVAL, and no launch, for X % m != 0, Y % m != 0, X / m != Y / m, m < 1, Tc < n_steps, t outside [0, n_steps);
+ *   FFNO_EUNSUPPORTED for m > 4096.
+ *
+ * ffno_markov_corr_metrics -- one launch after the loop; s_k = the S partials of sums[t][b][.][k] added in slice order:
+ *   metrics[2 + t] p_2[t] = mean_b s2 / (sqrt(s0) sqrt(s1))
+ *   metrics[0] diverged_t = first t with p_2[t] < threshold, n_steps if none (as a float)       metrics[1] mean_t p_2[t]
+ *   metrics holds 2 + n_steps floats; the routine places them behind those of ffno_markov_traj_metrics, in the same host read.
+ * --------------------------------------------------------------------------------------------- */
+size_t ffno_vorticity_coarsen_ws_floats(int B, int m, int n_steps);
+int ffno_vorticity_coarsen_step(const float* vel, const float* corr, float* preds2, float* sums, int B, int X, int Y, int m,
+                                int Tc, int n_steps, int t, float len_x, float len_y, void* stream);
+int ffno_markov_corr_metrics(const float* sums, float* metrics, int B, int m, int n_steps, float threshold, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Feedback of one rollout step of the Markov routine (the loop body of routines/grid_2d_markov.py:263-321 between two forward
