@@ -12,7 +12,9 @@ import torch
 
 import oracle_util as ou
 import pointcloud_model_oracle as pmo
-from backend_util import host_device, rel_l2  # noqa: F401  (host_device is a fixture)
+import test_kernels_iphi as tki
+import test_kernels_pchead as tkp
+from backend_util import Backend, host_device, rel_l2  # noqa: F401  (host_device is a fixture)
 
 B, W, M1, M2, S1, S2, N = 2, 32, 4, 3, 10, 12, 37      # unequal modes and grid axes catch swaps; 37 points: a ragged tile
 IPHI_W = 16
@@ -197,6 +199,48 @@ def test_iphi_refuses_a_coordinate_gradient(host_device):
     xi = iphi(x, torch.zeros(1, 42, device=host_device))
     with pytest.raises(RuntimeError, match="input coordinates"):
         xi.sum().backward()
+
+
+def test_autograd_wrappers_match_the_c_abi_over_slices_and_passes(host_device):
+    """ops.iphi_forward at two gradient slices (width 16, 2 x 530 points) and ops.point_head at 132 tiles (W = 32, 3 x 2757
+    points) under torch.autograd give the bits of the direct C ABI calls of test_kernels_iphi.py / test_kernels_pchead.py on the
+    same inputs: _IPhiFn.backward and _PointHeadFn.backward size their workspaces for the slice and split counts the kernels
+    use, and hand over the same buffers in the same order."""
+    from fourierflow_amd import ops
+    be = Backend("emu" if host_device == "cpu" else "gpu")
+    dev = lambda a, grad=False: torch.tensor(a, device=host_device).requires_grad_(grad)   # noqa: E731
+
+    width, b, n = tki.MULTI_SLICE[0]
+    sd, x, code, dxi = tki._inputs(width, b, n, 200 + width)
+    hp, par, hx, hc, xi, feat, acts = tki._forward(be, sd, x, code, width, True)
+    grads, dcode, _ = tki.iphi_backward(be, par, hx, hc, feat, acts, sd, dxi, width)
+    params = [dev(sd[k], True) for k in pmo.IPHI_NAMES]
+    ct = dev(code, True)
+    out = ops.iphi_forward(dev(x), ct, width, params)
+    np.testing.assert_array_equal(out.detach().cpu().numpy(), be.get(xi))
+    got = torch.autograd.grad(out, [ct] + params, dev(dxi))
+    np.testing.assert_array_equal(got[0].cpu().numpy(), dcode)
+    for k, g in zip(pmo.IPHI_NAMES, got[1:]):
+        np.testing.assert_array_equal(g.cpu().numpy(), grads[k], err_msg=k)
+
+    w, b, n, o = tkp.MULTI_PASS[0]
+    sd, t, x, dy = tkp._inputs(w, b, n, o, 300 + w + n)
+    par, ht, hx, y, pre = tkp.pchead_forward(be, sd, t, x, o)
+    dt, grads, _ = tkp.pchead_backward(be, par, ht, hx, pre, sd, dy)
+    bs, fc1, fc2 = torch.nn.Conv1d(2, w, 1), torch.nn.Linear(w, 128), torch.nn.Linear(128, o)
+    with torch.no_grad():
+        bs.weight.copy_(torch.tensor(sd["bs.weight"]).reshape(w, 2, 1)), bs.bias.copy_(torch.tensor(sd["bs.bias"]))
+        fc1.weight.copy_(torch.tensor(sd["fc1.weight"])), fc1.bias.copy_(torch.tensor(sd["fc1.bias"]))
+        fc2.weight.copy_(torch.tensor(sd["fc2.weight"])), fc2.bias.copy_(torch.tensor(sd["fc2.bias"]))
+    bs.to(host_device), fc1.to(host_device), fc2.to(host_device)
+    tt = dev(t, True)
+    out = ops.point_head(tt, dev(x), bs, fc1, fc2)
+    np.testing.assert_array_equal(out.detach().cpu().numpy(), be.get(y))
+    mods = [bs.weight, bs.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias]
+    got = torch.autograd.grad(out, [tt] + mods, dev(dy))
+    np.testing.assert_array_equal(got[0].cpu().numpy(), dt)
+    for k, g in zip(pmo.HEAD_NAMES, got[1:]):
+        np.testing.assert_array_equal(g.cpu().numpy().reshape(grads[k].shape), grads[k], err_msg=k)
 
 
 @pytest.mark.gpu
