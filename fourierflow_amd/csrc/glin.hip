@@ -4,8 +4,8 @@
 // configuration every shipped experiment uses: n_layers = 2, dropout = 0.  The reference class is more general --
 //     for i in range(n_layers):  Linear(dim | dim*factor -> dim*factor | dim), Dropout(p), ReLU (all but the last), [LayerNorm]
 // -- and FNOFactorized2DBlock adds Dropout(in_dropout) after in_proj (grid_2d.py:113,158).  These kernels are that general path:
-// one layer per launch, hidden activations kept in HBM for the backward pass, any (Cin, Cout) that is a multiple of 32 up to
-// 256, exact fp32 arithmetic (v_mfma_f32_32x32x2_f32 is an fmaf chain), and dropout as a counter-based mask that the backward
+// one layer per launch, hidden activations kept in HBM for the backward pass, any Cin and Cout from 1 to 256 (tiles and K chunks are
+// zero padded), exact fp32 arithmetic (v_mfma_f32_32x32x2_f32 is an fmaf chain), and dropout as a counter-based mask that the backward
 // pass REGENERATES from (seed, element index) instead of storing:
 //     fwd          out[p][o] = keep(p, o) / (1 - p_drop) * act(b[o] + sum_i W[o][i] x[p][i])  (+ resid[p][o])
 //                  (Linear -> Dropout -> ReLU of the reference: the positive dropout scale commutes with the ReLU)

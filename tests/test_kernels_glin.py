@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from backend_util import be, rel_l2  # noqa: F401
+from step_models import keep_model
 
 TOL = 1e-5
 
@@ -20,6 +21,12 @@ def keep_mask(be, shape, p, seed):
 def test_glin_fwd_bwd(be, P, Cin, Cout, p_drop):
     if be.kind == "emu" and P > 1000:
         pytest.skip("large case runs on the GPU only")
+    seed = 1234 + P
+    glin_fwd_bwd(be, P, Cin, Cout, p_drop, seed, keep_mask(be, (P, Cout), p_drop, seed) if p_drop else np.ones((P, Cout)))
+
+
+def glin_fwd_bwd(be, P, Cin, Cout, p_drop, seed, keep):
+    """Both layer kinds forward, their data and weight gradients, against fp64 numpy with `keep` as the dropout mask."""
     lib, p = be.lib, be.ptr
     rs = np.random.RandomState(P + Cin + Cout)
     x = rs.standard_normal((P, Cin)).astype(np.float32)
@@ -27,9 +34,7 @@ def test_glin_fwd_bwd(be, P, Cin, Cout, p_drop):
     b = (rs.standard_normal(Cout) * 0.1).astype(np.float32)
     resid = rs.standard_normal((P, Cout)).astype(np.float32)
     g = rs.standard_normal((P, Cout)).astype(np.float32)
-    seed = 1234 + P
     dx_, dW_, db_ = be.put(x), be.put(W), be.put(b)
-    keep = keep_mask(be, (P, Cout), p_drop, seed) if p_drop else np.ones((P, Cout))
     if p_drop:
         assert abs(keep.mean() - (1 - p_drop)) < 4 * np.sqrt(p_drop * (1 - p_drop) / keep.size) + 1e-3      # a fair coin of bias p
     sc = 1.0 / (1.0 - p_drop)
@@ -58,6 +63,34 @@ def test_glin_fwd_bwd(be, P, Cin, Cout, p_drop):
             assert lib.ffno_glin_bwd_weights(p(dg), p(yb), p(dx_), p(part), p(gW), p(gb), P, Cin, Cout, p_drop, seed, acc, None) == 0
         assert rel_l2(be.get(gW), 2 * dpre.T @ x.astype(np.float64)) < TOL
         assert rel_l2(be.get(gb), 2 * dpre.sum(0)) < TOL
+
+
+# (P, Cin, Cout) off the 64 x 64 tile and the K chunk of 32: Cin below one chunk, a single output column, Cin and Cout past whole
+# tiles, and P where the weight-gradient split count turns from 1 to 2 (2049: the second slice's last chunk holds one pixel)
+@pytest.mark.parametrize("P,Cin,Cout", [(70, 3, 64), (33, 40, 1), (65, 200, 72), (2049, 32, 33), (2081, 5, 7)])
+@pytest.mark.parametrize("p_drop", [0.0, 0.3])
+def test_glin_off_tile_shapes_with_the_model_mask(be, P, Cin, Cout, p_drop):
+    """As test_glin_fwd_bwd, but the dropout mask of the reference is tests/step_models.keep_model, not the kernel's own export."""
+    assert be.lib.ffno_glin_supported(Cin, Cout) == 1
+    assert be.lib.ffno_glin_wgrad_nsplit(P) == (2 if P > 2048 else 1) and be.lib.ffno_glin_wgrad_nsplit(2048) == 1
+    seed = 4321 + P
+    keep = keep_model(P * Cout, p_drop, seed).reshape(P, Cout).astype(np.float64) if p_drop else np.ones((P, Cout))
+    glin_fwd_bwd(be, P, Cin, Cout, p_drop, seed, keep)
+
+
+def test_dropout_in_place_past_one_grid(be):
+    """n = 300 001 is more than the 4 * CU workgroups of 256 elements that a 256-CU device launches: the stride loop's second pass."""
+    lib, p = be.lib, be.ptr
+    n, p_drop, seed = 300001, 0.3, 99
+    x = np.random.RandomState(5).standard_normal(n).astype(np.float32)
+    dx = be.put(x)
+    assert lib.ffno_dropout(p(dx), n, p_drop, seed, None) == 0
+    keep = keep_model(n, p_drop, seed)
+    got = np.asarray(be.get(dx))
+    assert np.array_equal(got[~keep], np.zeros(int((~keep).sum()), np.float32)) and np.all(x[keep] != 0)
+    # kept: x * scale with scale = 1.f / (1.f - p): the roundings of 1 - p, of the quotient and of the product, 2^-24 each
+    want = x[keep].astype(np.float64) / (1.0 - float(np.float32(p_drop)))
+    np.testing.assert_allclose(got[keep], want, rtol=2.0 ** -22, atol=0)
 
 
 def test_dropout_in_place_and_argument_checks(be):

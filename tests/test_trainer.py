@@ -40,6 +40,38 @@ def test_train_steps_match_reference_golden(host_device):
                p.data_ptr() < tr.pflat.data_ptr() + tr.pflat.numel() * 4 for p in blk.parameters())
 
 
+DECAY_BOUND = 4 * 1.25e-4      # measured 1.244e-4 (emulator) / 1.219e-4 (MI355X): test_trainer_hands_weight_decay_to_the_kernel
+
+
+def test_trainer_hands_weight_decay_to_the_kernel(host_device):
+    """Two trainers on the same block state and batch, weight_decay 0.1 and 0, no warm-up (so the first step's lr is not 0).
+    AdamW's decay is decoupled: the moments and the Adam term are the same in both, and after one step
+        p(wd) - p(0) = -lr wd p0
+    over the whole flat buffer.  Both parameter sets are rounded to fp32 (2^-24 |p| each) and their difference is
+    lr wd = 2.5e-4 of |p|, so the rel-L2 of the difference against the fp64 expression is of the order 2^-24 / 2.5e-4 = 2e-4.
+    (The kernel's fp32 factor 1 - lr wd adds a common relative error of up to 2^-24 / 2.5e-4 as well.)
+    Measured: emulator 1.244e-4, MI355X 1.219e-4; DECAY_BOUND is four times the larger."""
+    from fourierflow_amd.modules import FNOFactorized2DBlock
+    from fourierflow_amd.trainer import FFNOTrainer
+    g = gu.load_golden("train_c64_2l")
+    kw = gu.golden_kwargs(g)
+    B, M, N, seed, _ = [int(v) for v in g["meta"]]
+    x_np, t_np = gu.make_block_io(kw, seed + 1, B, M, N)
+    lr, wd = 2.5e-3, 0.1
+    after = []
+    for decay in (wd, 0.0):
+        blk = FNOFactorized2DBlock(**kw)
+        blk.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in gu.make_block_state_dict(kw, seed).items()})
+        tr = FFNOTrainer(blk.to(host_device), lr=lr, weight_decay=decay, num_warmup_steps=0, num_training_steps=10)
+        assert tr.current_lr() == lr
+        p0 = tr.pflat.detach().cpu().numpy().astype(np.float64)
+        tr.train_step(torch.from_numpy(x_np).to(host_device), torch.from_numpy(t_np).to(host_device))
+        after.append(tr.pflat.detach().cpu().numpy().astype(np.float64))
+    err = rel_l2(after[0] - after[1], -float(np.float32(lr)) * float(np.float32(wd)) * p0)
+    print(f"\ntrainer decay {host_device}: rel-L2 of p(wd) - p(0) against -lr wd p0 {err:.3e}")
+    assert err < DECAY_BOUND, err
+
+
 @pytest.mark.parametrize("deferred,lazy,sched,layer_calls", [(False, "0", 0, True), (True, "0", 3, True), (True, "s", 2, True),
                                                              (True, "s", 3, False), (True, "s", 0, False)])
 def test_train_steps_match_golden_under_every_backward_schedule(host_device, deferred, lazy, sched, layer_calls):
