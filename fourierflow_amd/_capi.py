@@ -306,6 +306,10 @@ SIGNATURES = {
     "ffno_ns2d_derivs": (I, [P, P, I, I, P]),
     "ffno_ns2d_advect": (I, [P, P, SZ, P]),
     "ffno_ns2d_cn_update": (I, [P, P, P, P, F, I, I, I, P]),
+    "ffno_kf2d_supported": (I, [I]),
+    "ffno_kf2d_derivs": (I, [P, P, F, I, I, P]),
+    "ffno_kf2d_stage": (I, [P, P, P, F, F, F, F, F, F, F, I, F, F, F, F, I, I, I, P]),
+    "ffno_kf2d_downsample": (I, [P, P, I, I, I, F, P]),
 }
 
 

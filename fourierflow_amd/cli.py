@@ -1,6 +1,7 @@
 """`python -m fourierflow_amd {train,test,predict} CONFIG.yaml [overrides...]`, `python -m fourierflow_amd rollout CONFIG.yaml
 --init IC.npz` (the trained Markov model as a simulator, see `rollout` below) and `python -m fourierflow_amd generate
-navier-stokes PATH` (the data the 2-D Navier-Stokes configs train on, see `navier_stokes` below) -- the command surface of the reference
+navier-stokes PATH` / `generate kolmogorov X.yaml` (the data the 2-D Navier-Stokes and the Kolmogorov-flow configs train on, see
+`navier_stokes` and `kolmogorov` below) -- the command surface of the reference
 (`fourierflow train | test | predict | infer`, reference commands/train.py:27-148, commands/test.py:24-90,
 commands/predict.py:24-110, commands/infer.py) for the routines built here, with the same positional arguments and flag names
 (``--force --resume --checkpoint-id --trial --debug --no-logging --map-location``) and the same on-disk layout:
@@ -782,12 +783,22 @@ class _NpzStream:
         self.out, self.rows, self.arrays = out, rows, {}
         self.scratch = tempfile.mkdtemp(prefix=os.path.basename(out) + ".", dir=os.path.dirname(out) or ".")
 
-    def put(self, name: str, row: int, block: np.ndarray):
+    def array(self, name: str, tail) -> np.ndarray:
+        """The memory-mapped array ``name`` [rows, *tail], created on first use."""
         import os
         if name not in self.arrays:
             self.arrays[name] = np.lib.format.open_memmap(os.path.join(self.scratch, name + ".npy"), mode="w+", dtype=np.float32,
-                                                          shape=(self.rows, *block.shape[1:]))
-        self.arrays[name][row:row + len(block)] = block
+                                                          shape=(self.rows, *tail))
+        return self.arrays[name]
+
+    def put(self, name: str, row: int, block: np.ndarray):
+        self.array(name, block.shape[1:])[row:row + len(block)] = block
+
+    def abort(self):
+        """Drop what was written so far; no .npz is made."""
+        import shutil
+        self.arrays.clear()
+        shutil.rmtree(self.scratch, ignore_errors=True)
 
     def close(self) -> Dict[str, List[int]]:
         import os
@@ -881,6 +892,29 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
             done += b
         written[split] = dict(file=sink.out, trajectories=n, **sink.close())
     print(json.dumps(dict(solver_steps=n_solver, delta=delta, grid=s, ssr=ssr, **written)), flush=True)
+
+
+@generate_app.command("kolmogorov")
+def kolmogorov(config_path: Path = Argument(..., help="a data-generation YAML of the reference's data/kolmogorov tree"),
+               overrides: Optional[List[str]] = Argument(None, help="a.b=c overrides of the YAML, e.g. sim_grid.shape=[256,256]"),
+               batch_size: int = Option(1, help="trajectories solved at once"),
+               device: Optional[str] = Option(None, hidden=True)):
+    """Generate 2-D Kolmogorov flows (the reference's `fourierflow generate kolmogorov`): the pseudo-spectral solver with
+    Crank-Nicolson / RK4 time stepping, Kolmogorov forcing and drag that CONFIG describes, written beside CONFIG as the .npz files
+    KolmogorovBuilder reads in place of the reference's .nc files.  With warmup_steps > 0 (the initial_conditions files): the
+    final fields, STEM_{size}.npz holding vorticity [n, size, size].  Otherwise (the trajectories files, started from
+    `init_path`): STEM_{size}_{k}.npz holding vorticity [n, outer_steps // k, size, size], every k-th snapshot starting at the
+    k-th, and time.  Sizes below the simulation grid are reduced through the staggered velocity, as the reference does."""
+    from typer import BadParameter
+
+    from .builders.kolmogorov_flow import generate_kolmogorov, plan_kolmogorov
+    if batch_size < 1:
+        raise BadParameter("--batch-size is at least 1")
+    plan = plan_kolmogorov(load_config(str(config_path), overrides or []), str(config_path))
+    t0 = time.perf_counter()
+    written = generate_kolmogorov(plan, _device(device), batch_size, _NpzStream)
+    print(json.dumps(dict(dt=plan.dt, steps=plan.solver_steps, grid=plan.N, trajectories=plan.n_trajectories,
+                          elapsed=time.perf_counter() - t0, files=written)), flush=True)
 
 
 def main():

@@ -291,3 +291,5 @@ extern "C" int ffno_fw3d_grad_reduce(const float* partial, float* g1, float* g2,
 #include "ffno_pchead.h"
 // the streaming kernels of the Navier-Stokes data generator's solver step (entry points ffno_ns2d_*)
 #include "ffno_ns2d.h"
+// the streaming and downsampling kernels of the Kolmogorov-flow data generator's time step (entry points ffno_kf2d_*)
+#include "ffno_kf2d.h"

@@ -1184,6 +1184,41 @@ int ffno_ns2d_advect(const float* fields4, float* out, size_t n, void* stream);
 int ffno_ns2d_cn_update(float* w_h, const float* F_h, const float* f_h, const float* visc, float delta_t, int f_batched, int B,
                         int N, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The time step of the pseudo-spectral Kolmogorov-flow solver behind `generate kolmogorov` (reference builders/kolmogorov.py:328-428
+ * with jax-cfd's spectral NavierStokes2D under crank_nicolson_rk4; written from the formulas), fp32, on
+ * torch.fft.rfft2 half spectra s[B][N][N/2+1][2] of the vorticity on the periodic square [0, 2 pi / k0)^2.  N a power of two,
+ * 16 <= N <= 4096 (ffno_kf2d_supported); B N (N/2+1) < 2^31; 0 < k0 < 1e6; every spectrum 16-byte aligned (FFNO_EINVAL otherwise).
+ * Row r is k_x = k0 r (r < N/2) or k0 (r - N), column c is k_y = k0 c; k0 = 1 (the domain [0, 2 pi)^2) gives integer
+ * wavenumbers.  One step is five stages s = 0..4 of  derivs -> irfft2 of out4 -> ffno_ns2d_advect -> rfft2 -> stage;  the FFTs
+ * are the caller's (rocFFT).
+ *   ffno_kf2d_derivs: out4[4][B][N][N/2+1][2] = the spectra of
+ *         v_x = i k_y psi_h,  v_y = -i k_x psi_h,  w_x = i k_x w_h,  w_y = i k_y w_h,     psi_h = w_h / |k|^2, psi_h(0,0) = 0.
+ *       Row N/2 of v_y and w_x and column N/2 of v_x and w_y are written as zeros (a derivative along an axis has no Nyquist
+ *       bin, as in ffno_ns2d_derivs).
+ *   ffno_kf2d_stage: w_h and h in place, adv_h (the spectrum of v_x w_x + v_y w_y) only read:
+ *         h   <- -filt adv_scale adv_h + linear_coefficient w_h + f_h + beta h  (first != 0: h is not read, beta is ignored)
+ *         w_h <- (w_h + gamma dt h + mu L w_h) / (1 - mu L),                     L = -viscosity |k|^2 - drag
+ *       filt = 1 where 9 (r_x^2 + c^2) <= N^2 in bin indices (the circular 2/3 rule, exact for these N), else 0.  f_h is zero but
+ *       in bin (row 0, column kf) of every sample, where it is (f_re, f_im); kf = 0 means no forcing (then f_re = f_im = 0),
+ *       kf outside 0 ... N/2 - 1 is FFNO_EINVAL.  For the Kolmogorov forcing -magnitude k cos(k y) sampled at the cell centres
+ *       y_j = (j + 1/2) len / N the host passes kf = k / k0 and f = -magnitude k (N^2 / 2) e^{i pi kf / N}.
+ *       adv_scale > 0: 1, or N^-4 (exact, N a power of two) when the caller left the 1 / N^2 out of the inverse transforms
+ *       of the two factors of every product.  The Carpenter-Kennedy coefficients and mu_s = dt (alpha_{s+1} - alpha_s) / 2 are the caller's.
+ *   ffno_kf2d_downsample: vel2[2][B][N][N] (v_x, v_y on the grid) -> out[B][m][m], m a divisor of N (FFNO_EINVAL otherwise),
+ *       B <= 65535: with f = N / m and d = length / m
+ *         u_c[i][j] = (sum_{b<f} v_x[f i + f-1][f j + b]) / f,      v_c[i][j] = (sum_{a<f} v_y[f i + a][f j + f-1]) / f,
+ *         out[i][j] = (v_c[(i+1) % m][j] - v_c[i][j]) / d - (u_c[i][(j+1) % m] - u_c[i][j]) / d
+ *       (jax-cfd's downsample_staggered_velocity and curl, as in ffno_vorticity_coarsen_step); sums sequential in index order.
+ * Deterministic; no atomics, no workspace.
+ * --------------------------------------------------------------------------------------------- */
+int ffno_kf2d_supported(int N);
+int ffno_kf2d_derivs(const float* w_h, float* out4, float k0, int B, int N, void* stream);
+int ffno_kf2d_stage(float* w_h, float* h, const float* adv_h, float viscosity, float drag, float linear_coefficient, float dt,
+                    float beta, float gamma, float mu, int kf, float f_re, float f_im, float k0, float adv_scale, int first, int B,
+                    int N, void* stream);
+int ffno_kf2d_downsample(const float* vel2, float* out, int B, int N, int m, float length, void* stream);
+
 /* small utilities used by the host driver */
 int ffno_axpy(float* y, const float* x, float alpha, size_t n, void* stream); /* y += alpha*x */
 
