@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 9
+ABI_VERSION = 10
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -284,6 +284,8 @@ SIGNATURES = {
     "ffno_vorticity_coarsen_ws_floats": (SZ, [I, I, I]),
     "ffno_vorticity_coarsen_step": (I, [P, P, P, P, I, I, I, I, I, I, I, F, F, P]),
     "ffno_markov_corr_metrics": (I, [P, P, I, I, I, F, P]),
+    "ffno_prediction_export_step": (I, [P, P, P, P, I, I, I, I, I, I, F, F, P]),
+    "ffno_energy_spectrum": (I, [P, P, P, I, I, P]),
     "ffno_markov_advance": (I, [P, P, P, I, I, I, P]),
     "ffno_markov_pairs": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "ffno_markov_pairs_tf": (I, [P, P, P, P, P, P, P, I, P, P, P, I, I, I, I, I, I, I, I, P]),

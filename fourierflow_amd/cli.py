@@ -33,6 +33,11 @@ builder's ``inference_data()`` and reports the reference's ``inference_time``; N
 either, and is refused there.  With KolmogorovBuilder the routine reduces its predictions to the grid of ``corr_data`` on the device
 (``downsample_corr``), ``valid_corr`` / ``valid_reduced_time_until`` are the reduced ones, the checkpoint is selected by the config's
 ``CustomModelCheckpoint`` entry (``valid_time_until``, max) and `test --builder` also prints ``test_reduced_time_until``.
+
+``test CONFIG [--builder | --data TRAJ.npz] [--pred-path P]``: a Markov routine with a ``pred_path`` (the
+torus_kochkov/ffno/predictions configs set ``routine.pred_path``; ``--pred-path`` overrides it) exports every test prediction on its
+``pred_size`` grid -- vorticity, vx, vy and their energy spectrum (diagnostics.py) -- and the command writes ONE file for all test
+batches, the ``.npz`` sibling of the path, reporting ``pred_path`` (the file written) and ``pred_samples``.
 """
 from __future__ import annotations
 
@@ -222,10 +227,11 @@ def _instantiate_builder(cfg, kind: str, batch_size: Optional[int], routine=None
     return bld
 
 
-def _split_loss(routine, data, step: str = "validation_step", keys=None) -> Dict[str, float]:
+def _split_loss(routine, data, step: str = "validation_step", keys=None, each=None) -> Dict[str, float]:
     """The sample-weighted mean, over every batch of `data` (short last batch included), of every key that `step` logs -- what
     Lightning logs for the epoch -- under eval().  A routine whose step returns the loss alone gives {'valid_loss': ...}.  Tensor
-    values are accumulated on the device and read once at the end; `keys` picks from a step that returns more (per-step tables)."""
+    values are accumulated on the device and read once at the end; `keys` picks from a step that returns more (per-step tables);
+    `each`, where given, sees every batch's whole output."""
     was_training = routine.training
     routine.eval()
     try:
@@ -236,6 +242,8 @@ def _split_loss(routine, data, step: str = "validation_step", keys=None) -> Dict
                 out = getattr(routine, step)(batch)
                 if not isinstance(out, dict):
                     out = {"valid_loss": out}
+                if each is not None:
+                    each(out)
                 for k in (keys or out):
                     v = out[k]
                     part = (v.reshape(()).double() if torch.is_tensor(v) else float(v)) * B
@@ -244,6 +252,23 @@ def _split_loss(routine, data, step: str = "validation_step", keys=None) -> Dict
             return {k: float(v) / n for k, v in totals.items()}
     finally:
         routine.train(was_training)
+
+
+class _PredictionParts:
+    """The exported arrays of every test batch of a Markov routine with a pred_path, on the host, and the one file they make."""
+
+    def __init__(self, routine):
+        self.routine, self.parts, self.times = routine, [], None
+
+    def __call__(self, out):
+        from .diagnostics import PRED_KEYS
+        self.parts.append({k: out[k].cpu() for k in PRED_KEYS})
+        if self.times is None and "test_times" in out:
+            self.times = out["test_times"].cpu()
+
+    def write(self) -> Dict[str, object]:
+        path = self.routine.write_predictions(None, self.parts, self.times)
+        return dict(pred_path=path, pred_samples=sum(p["pred_vorticity"].shape[1] for p in self.parts))
 
 
 TEST_KEYS = {"markov": ("test_loss", "test_loss_avg", "test_time_until", "test_corr"),
@@ -553,8 +578,14 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
          builder: bool = Option(False, "--builder", help="the test metrics over the whole test split of the config's `builder` "
                                                          "section (KolmogorovBuilder: with test_reduced_time_until, on the grid "
                                                          "of its corr_data)"),
+         pred_path: Optional[Path] = Option(None, "--pred-path", help="write the test predictions of a Markov routine here (vorticity, "
+                                                                      "vx, vy on the routine's pred_size grid and their energy "
+                                                                      "spectrum, as the .npz sibling of the path): overrides the "
+                                                                      "config's routine.pred_path"),
          device: Optional[str] = Option(None, hidden=True)):
-    """Test: load the best checkpoint of the trial (or `checkpoint_path=...` override) and report the test metrics."""
+    """Test: load the best checkpoint of the trial (or `checkpoint_path=...` override) and report the test metrics.  A Markov
+    routine with a pred_path (the torus_kochkov/ffno/predictions configs, or --pred-path) also writes its predictions, one file
+    for all test batches, and reports `pred_path` (the file written) and `pred_samples`."""
     if builder and data is not None:
         raise ValueError("--builder takes the test split from the config's builder section: it does not go with --data")
     cfg = load_config(str(config_path), overrides or [])
@@ -565,17 +596,30 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
     routine.load_lightning_model_state(str(ckpt), map_location)
     routine.to(dev)
     routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
+    if pred_path is not None:
+        if kind != "markov":
+            raise ValueError(f"--pred-path writes the test predictions of Grid2DMarkovExperiment; this config's routine is "
+                             f"{type(routine).__name__}")
+        routine.pred_path = str(pred_path)
+    parts = _PredictionParts(routine) if getattr(routine, "pred_path", None) is not None else None
     if builder:
         bld = _instantiate_builder(cfg, kind, batch_size, routine)
         test_set = bld.test_data(dev)
         if kind in TEST_KEYS:
             reduced = ("test_reduced_time_until",) if type(bld).__name__ == "KolmogorovBuilder" else ()
-            m = _split_loss(routine, test_set, "test_step", TEST_KEYS[kind] + reduced)
+            m = _split_loss(routine, test_set, "test_step", TEST_KEYS[kind] + reduced, each=parts)
         else:
             m = dict(test_loss=_split_loss(routine, test_set)["valid_loss"])
-        print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in m.items()}, samples=test_set.n)), flush=True)
+        written = parts.write() if parts is not None else {}
+        print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in m.items()}, samples=test_set.n, **written)),
+              flush=True)
         return
     src = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial)
+    if parts is not None and not src.trajectories:      # one-step pairs or synthetic fields: test_step, which exports, does not run
+        if pred_path is not None:
+            raise ValueError("--pred-path: the predictions come from the trajectory rollout of test_step; give `--data TRAJ.npz` "
+                             "holding data [n, M, N, T], or --builder")
+        parts = None
     it = iter(src)
     acc: Dict[str, float] = {}
     for _ in range(batches):
@@ -583,13 +627,16 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
         if kind == "rollout":
             m = {k: v for k, v in routine.test_step(b).items() if k in ("test_loss", "test_loss_avg", "test_time_until")}
         elif src.trajectories:      # the reference's test metrics of the Markov routine (:408-416)
-            m = {k: v for k, v in routine.test_step(b).items()
-                 if k in ("test_loss", "test_loss_avg", "test_time_until", "test_corr")}
+            out = routine.test_step(b)
+            if parts is not None:
+                parts(out)
+            m = {k: v for k, v in out.items() if k in ("test_loss", "test_loss_avg", "test_time_until", "test_corr")}
         else:
             m = {"test_loss": _valid_loss(routine, kind, b)}
         for k, v in m.items():
             acc[k] = acc.get(k, 0.0) + float(v) / batches
-    print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in acc.items()})), flush=True)
+    written = parts.write() if parts is not None else {}
+    print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in acc.items()}, **written)), flush=True)
 
 
 @app.command()

@@ -175,3 +175,8 @@ extern "C" int ffno_velocity_features(const float* vorticity, float* out, float*
 // the reduction of a velocity image to the grid of corr_data and its correlation sums (entry points ffno_vorticity_coarsen_*,
 // ffno_markov_corr_metrics): what the validation of the torus_kochkov configs runs on the output of the launch above
 #include "ffno_coarsen.h"
+
+// the export of a prediction's vorticity and velocity on the pred_size grid and the energy spectrum of the exported velocities
+// (entry points ffno_prediction_export_step, ffno_energy_spectrum): what the test of the torus_kochkov/ffno/predictions configs
+// runs on the output of ffno_velocity_features
+#include "ffno_pred_export.h"

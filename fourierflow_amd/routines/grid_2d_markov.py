@@ -4,7 +4,9 @@ without Lightning / wandb / jax: feature build (positional channels, running nor
 the operator, inverse-normalise + relative-L2 loss, the manual optimisation step
 (routines/base.py:27-52), epoch-0 statistics accumulation, the autoregressive rollout used by predict/infer, and the
 trajectory validation / test metrics of ``_valid_step`` / ``compute_losses`` / ``validation_step`` / ``test_step`` (:195-416),
-with ``downsample_corr=True`` including the correlation on the reduced grid of ``corr_data`` (:350-370, utils/array.py:18-80).
+with ``downsample_corr=True`` including the correlation on the reduced grid of ``corr_data`` (:350-370, utils/array.py:18-80),
+and with ``pred_path`` the export of the test predictions (:427-476): vorticity, vx, vy on the ``pred_size`` grid and their energy
+spectrum, returned by ``test_step`` and written by ``write_predictions``.
 
 Everything on the device is a HIP kernel of libffno_hip.so; torch supplies memory, the stream and the
 Gaussian noise samples.
@@ -19,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _capi, _lib
+from .. import _capi, _lib, diagnostics
 from ..engine import _p
 from ..modules.normalizer import Normalizer
 from ..trainer import FFNOTrainer
@@ -33,7 +35,7 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                  noise_std: float = 0.0, shuffle_grid: bool = False, use_velocity: bool = False,
                  learn_difference: bool = False, step_size: float = 1.0, optimizer: Optional[dict] = None,
                  scheduler: Optional[dict] = None, domain=((0.0, 2 * math.pi), (0.0, 2 * math.pi)), grid_size=(64,),
-                 downsample_corr: bool = False, **unused):
+                 downsample_corr: bool = False, pred_path: Optional[str] = None, pred_size: int = 64, **unused):
         super().__init__()
         reject_unsupported_routine_kwargs(unused)
         if use_fourier_position:
@@ -69,6 +71,10 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         # corr_data of another grid size than the model's: reduce every prediction to it on the device (ffno_vorticity_coarsen_step)
         # where the reference calls downsample_vorticity; off, such a batch is refused as before
         self.downsample_corr = bool(downsample_corr)
+        # the reference's argument: with it, test_step also exports every prediction on the pred_size x pred_size grid (the
+        # reference's hard-coded 64: :433) with its energy spectrum; write_predictions writes them.  validation_step never does.
+        self.pred_path = None if pred_path is None else str(pred_path)
+        self.pred_size = diagnostics.check_size(pred_size, "pred_size")
         self._opt_kw = dict(lr=2.5e-3, weight_decay=1e-4)
         self._opt_kw.update(optimizer or {})
         # the F-FNO configs run cosine-with-warm-up per step; the FNOZongyi2DBlock ablations (torus_li/ablation/zongyi_markov*)
@@ -330,12 +336,14 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         return B, M, N, T, n_steps
 
     @torch.no_grad()
-    def _valid_step(self, batch: Dict[str, torch.Tensor]):
+    def _valid_step(self, batch: Dict[str, torch.Tensor], export: bool = False):
         """Autoregressive rollout over batch['data'] [B, M, N, T] from data[..., T - n_steps - 1] (:195-326) ->
         (summed step loss, step_losses [n_steps], preds [B, M, N, n_steps], []).  No noise, no statistics accumulation.  Per step:
         the feature kernel, the inference engine, one ffno_markov_traj_step launch (inverse normalisation, difference
         update, next input, preds column and the sums of every metric); ffno_markov_traj_metrics after the loop.  The last
-        entry is the reference's `forecast_list` per step, which the inference engine does not produce."""
+        entry is the reference's `forecast_list` per step, which the inference engine does not produce.  With `export` (test_step of a
+        routine with a pred_path) every step also makes one ffno_prediction_export_step launch on the velocity image of its
+        prediction, and one batched rfft2 with one ffno_energy_spectrum launch follows the loop: `self._pred`."""
         data = batch['data'].contiguous().float()
         _lib.require_device_tensor(data, "batch['data']")
         B, M, N, T, n_steps = self._traj_geometry(data)
@@ -351,6 +359,7 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         metrics = torch.empty(4 + 2 * n_steps + (2 + n_steps if corr is not None else 0), dtype=torch.float32, device=dev)
         sums2 = self._coarsen_sums(corr, B, n_steps)
         preds = torch.empty(B, M, N, n_steps, dtype=torch.float32, device=dev)
+        slabs = self._export_slabs(B, M, N, n_steps, dev) if export else None
         im = data[..., T - n_steps - 1].unsqueeze(-1).contiguous()      # the first input; then every prediction, in place
         prev = _p(im) if self.learn_difference else None                 # prev_im is the running field itself (:316-318)
         tr = self.trainer()
@@ -368,9 +377,12 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
                     raise ValueError(f"the rollout feeds one predicted channel back, conv returned {tuple(out.shape)}")
                 _capi.check(lib.ffno_markov_traj_step(_p(out), _p(affine), prev, _p(data), _p(im), _p(preds), _p(sums),
                                                       B, M, N, T, n_steps, t, stream), "markov_traj_step")
-                if corr is not None:      # the velocity image of this prediction: reduced here, and the next step's features
-                    vel = self._velocity(im)
-                    self._coarsen_step(vel, corr, sums2, n_steps, t)
+                if corr is not None or slabs is not None:      # the velocity image of this prediction, computed once: reduced
+                    vel = self._velocity(im)                   # and exported here, and the next step's features
+                    if corr is not None:
+                        self._coarsen_step(vel, corr, sums2, n_steps, t)
+                    if slabs is not None:
+                        self._export_step(vel, slabs, n_steps, t)
                     if not self.use_velocity:
                         vel = None
         finally:
@@ -379,6 +391,9 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         if corr is not None:
             self._corr_metrics(sums2, metrics, corr, B, n_steps)
         self._traj = (preds, metrics, corr is not None)
+        self._pred = None
+        if slabs is not None:      # [3][n_steps][B][m][m]: vorticity, vx, vy
+            self._pred = dict(zip(diagnostics.PRED_KEYS, (*slabs.unbind(0), diagnostics._spectrum_of_pair(slabs[1:]))))
         step_losses = metrics[4:4 + n_steps]
         return step_losses.sum(), step_losses, preds, []
 
@@ -471,8 +486,33 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         _capi.check(_lib.get_lib().ffno_markov_corr_metrics(_p(sums2), tail, B, corr.shape[1], n_steps, 0.95,
                                                             _lib.current_stream(metrics.device)), "markov_corr_metrics")
 
-    def _trajectory_metrics(self, batch):
-        loss, step_losses, preds, _ = self._valid_step(batch)
+    # -- the export behind pred_path (:427-476) ----------------------------------------------------------------------------------
+    def _export_slabs(self, B: int, M: int, N: int, n_steps: int, dev) -> torch.Tensor:
+        m = self.pred_size
+        if M % m or N % m or M // m != N // m:
+            raise ValueError(f"pred_path: a {M} x {N} prediction is exported on the {m} x {m} grid of pred_size={m} by an integer "
+                             f"factor, the same in both directions, and {M} / {m}, {N} / {m} is none (the reference writes a file "
+                             f"with the axes of a 64 x 64 grid whatever the model's)")
+        return torch.empty(3, n_steps, B, m, m, dtype=torch.float32, device=dev)
+
+    def _export_step(self, vel: torch.Tensor, slabs: torch.Tensor, n_steps: int, t: int):
+        B, M, N, _ = vel.shape
+        lx, ly = self.domain[0][1] - self.domain[0][0], self.domain[1][1] - self.domain[1][0]
+        _capi.check(_lib.get_lib().ffno_prediction_export_step(_p(vel), _p(slabs[0]), _p(slabs[1]), _p(slabs[2]), B, M, N,
+                                                               self.pred_size, n_steps, t, lx, ly,
+                                                               _lib.current_stream(vel.device)), "prediction_export_step")
+
+    def write_predictions(self, path: Optional[str], parts, times=None) -> str:
+        """The `pred_*` arrays of the test batches `parts` as one file, the .npz sibling of `path` (default: this routine's
+        pred_path): diagnostics.write_predictions with this routine's domain and step size.  The reference's test_step overwrites
+        its file with every batch, so that only the last batch survives; here writing is a step of its own, once per split."""
+        path = self.pred_path if path is None else path
+        if path is None:
+            raise ValueError("write_predictions needs a path: the routine was built without pred_path")
+        return diagnostics.write_predictions(path, parts, times, domain=self.domain, step_size=self.step_size)
+
+    def _trajectory_metrics(self, batch, export: bool = False):
+        loss, step_losses, preds, _ = self._valid_step(batch, export)
         loss, loss_full, time_until, reduced, p, times = self.compute_losses(batch, loss, preds)
         return loss, loss_full, time_until, reduced, p, times, step_losses
 
@@ -490,11 +530,15 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
 
     def test_step(self, batch, batch_idx: int = 0):
         """The reference's logged test keys (:408-425); its two wandb tables are returned as `test_correlations` (p per step)
-        and `test_losses` (relative-L2 per step), with `test_times` when the batch carries `times`."""
-        loss, loss_full, time_until, reduced, p, times, step_losses = self._trajectory_metrics(batch)
+        and `test_losses` (relative-L2 per step), with `test_times` when the batch carries `times`.  A routine with a pred_path
+        adds pred_vorticity, pred_vx, pred_vy [n_steps, B, pred_size, pred_size] and pred_energy_spectrum
+        [n_steps, B, pred_size / 2 + 1], device tensors (:427-476); it writes nothing -- see write_predictions."""
+        loss, loss_full, time_until, reduced, p, times, step_losses = self._trajectory_metrics(batch, self.pred_path is not None)
         out = {'test_loss_avg': loss, 'test_loss': loss_full, 'test_time_until': time_until,
                'test_reduced_time_until': reduced, 'test_corr': self.last_corr,
                'test_correlations': p, 'test_losses': step_losses}
         if times is not None:
             out['test_times'] = times
+        if self._pred is not None:
+            out.update(self._pred)
         return out

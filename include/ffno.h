@@ -80,8 +80,9 @@ const char* ffno_build_target(void);
  * library under newer host code would have read shifted arguments).  ffno_abi_version() returns the value the LIBRARY was built
  * with; a caller compares it with the FFNO_ABI_VERSION it was compiled against before the first compute call (the Python host
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
- * binds at load -- a library of generation 8 lacks them. */
-#define FFNO_ABI_VERSION 9
+ * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
+ * in the same way. */
+#define FFNO_ABI_VERSION 10
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -907,6 +908,41 @@ size_t ffno_vorticity_coarsen_ws_floats(int B, int m, int n_steps);
 int ffno_vorticity_coarsen_step(const float* vel, const float* corr, float* preds2, float* sums, int B, int X, int Y, int m,
                                 int Tc, int n_steps, int t, float len_x, float len_y, void* stream);
 int ffno_markov_corr_metrics(const float* sums, float* metrics, int B, int m, int n_steps, float threshold, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Prediction export of the Markov routine's test (`pred_path`; routines/grid_2d_markov.py:427-476 with utils/array.py:50-80
+ * downsample_vorticity_hat -- jax-cfd on the CPU, a Python loop over batch and time): vorticity, vx, vy of every predicted step
+ * on the m x m grid that the written file holds (the reference's hard-coded 64 x 64).  fp32, no atomics, every output written once.
+ *
+ * ffno_prediction_export_step -- one launch per rollout step t.  vel [B][X][Y][3] is the output of ffno_velocity_features for the
+ * prediction of step t (vorticity, u, v).  vort, vx, vy are TIME-MAJOR, [n_steps][B][m][m]: the launch writes slab t of each and
+ * nothing else, so its stores are contiguous; the host transposes to the reference's (sample, x, y, time) when it writes the
+ * file.  f = X / m = Y / m is an integer >= 1:
+ *   f == 1 (the reference's else branch, :448-452): vort, vx, vy = channels 0, 1, 2 of vel, bit for bit.
+ *   f > 1  (downsample_vorticity_hat): with u_c, v_c, w_c of ffno_vorticity_coarsen_step above (the last line of each block of f,
+ *          the mean across the block a sequential sum in index order, forward differences with periodic wrap, dx = len_x / m,
+ *          dy = len_y / m):  vx = u_c, vy = v_c, vort = w_c.
+ *   FFNO_EINVAL, and no launch: null pointers, non-positive sizes or lengths, t outside [0, n_steps).
+ *   FFNO_EUNSUPPORTED: X % m != 0, Y % m != 0, X / m != Y / m, m > 4096 (the LDS rows of one workgroup), B > 65535.
+ *
+ * ffno_energy_spectrum -- the isotropic kinetic-energy spectrum of n_img velocity images, one launch (what commands/plot.py:256-306
+ * takes of the written file through jax-cfd's compute_summary_dataset; the definition below is this project's own).  u_h, v_h
+ * [n_img][m][m/2+1][2] are the UNNORMALISED torch.fft.rfft2 half spectra of vx, vy; E is [n_img][m/2+1].
+ *   Bin (row r, column c) has the integer wavenumbers kx = r < m/2 ? r : r - m, ky = c.
+ *   Its shell is the integer s with (2s-1)^2 <= 4 (kx^2 + ky^2) < (2s+1)^2, i.e. s - 1/2 <= |k| < s + 1/2, decided in integer
+ *   arithmetic (for s = 0 the left inequality, -1/2 <= |k|, holds for every bin and only the right one is tested).
+ *   Its Hermitian weight is h = 1 for c == 0 or c == m/2, else 2 (the mirrored bin that the half spectrum leaves out).
+ *   E[s] = sum over the bins of shell s of  h (|u_h|^2 + |v_h|^2) / (2 m^4),   s = 0 .. m/2.
+ *   Shells s > m/2 (the corners of the square) are left out; with them added back, sum_s E[s] is the mean of (u^2 + v^2) / 2 over
+ *   the image (Parseval).
+ * Deterministic, no atomics.  Summation order inside a shell: one wave of 64 lanes per shell; lane l adds the shell's bins of rows
+ * l, l + 64, l + 128, l + 192 in that order, within a row by ascending column, as one sequential fp32 sum; the 64 lane sums are
+ * added by the xor butterfly 32, 16, 8, 4, 2, 1; the factor 1 / (2 m^4) is applied last.
+ *   FFNO_EINVAL: null pointers, non-positive sizes.  FFNO_EUNSUPPORTED: m not a multiple of 8, or outside 8 ... 256.
+ * --------------------------------------------------------------------------------------------- */
+int ffno_prediction_export_step(const float* vel, float* vort, float* vx, float* vy, int B, int X, int Y, int m, int n_steps,
+                                int t, float len_x, float len_y, void* stream);
+int ffno_energy_spectrum(const float* u_h, const float* v_h, float* E, int n_img, int m, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Feedback of one rollout step of the Markov routine (the loop body of routines/grid_2d_markov.py:263-321 between two forward
