@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 10
+ABI_VERSION = 11
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -264,6 +264,8 @@ SIGNATURES = {
     "ffno_plin_wgrad_nsplit": (I, [L]),
     "ffno_plin_wgrad_partial_floats": (SZ, [L, I, I]),
     "ffno_plin_bwd_weights": (I, [P, I, P, P, I, P, P, P, L, I, I, I, I, P]),
+    "ffno_plin_pos_fwd": (I, [P, I, P, P, P, P, P, P, P, I, P, I, I, I, I, I, I, P]),
+    "ffno_plin_pos_bwd_weights": (I, [P, I, P, P, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
     "ffno_glin_supported": (I, [I, I]),
     "ffno_glin_fwd": (I, [P, P, P, P, P, L, I, I, I, F, C.c_uint32, P]),
     "ffno_glin_bwd_data": (I, [P, P, P, P, L, I, I, F, C.c_uint32, I, P]),

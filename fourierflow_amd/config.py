@@ -162,14 +162,15 @@ def build_routine(cfg: Dict[str, Any]):
     r.pop("scheduler", None)
     routine_kwargs = {}
     model_target = str((r.get("conv") or r.get("model") or {}).get("_target_", ""))
-    baseline = model_target.endswith(("FNOZongyi2DBlock", "FNOMesh2D", "FNOMesh3D"))     # the StepLR (and Adam) users built here
+    adam_users = ("FNOMesh2D", "FNOMesh3D", "FNOPointCloud2D")      # the geo-FNO baselines: torch.optim.Adam + StepLR
+    baseline = model_target.endswith(("FNOZongyi2DBlock",) + adam_users)     # the StepLR users built here
     if model_target.startswith("fourierflow.") and model_target not in TARGET_MAP:      # before the optimiser checks: name the model
         raise NotImplementedError(f"{model_target} has no MI355X-native counterpart in fourierflow_amd (see DESIGN.md section 7)")
     if opt is not None:
-        names = ("torch.optim.AdamW",) + (("torch.optim.Adam",) if model_target.endswith(("FNOMesh2D", "FNOMesh3D")) else ())
+        names = ("torch.optim.AdamW",) + (("torch.optim.Adam",) if model_target.endswith(adam_users) else ())
         if not isinstance(opt, Partial) or opt.func.name not in names:
-            raise NotImplementedError(f"only torch.optim.AdamW (and torch.optim.Adam for FNOMesh2D / FNOMesh3D) map to the fused flat "
-                                      f"optimiser kernel, got {opt}")
+            raise NotImplementedError(f"only torch.optim.AdamW (and torch.optim.Adam for FNOMesh2D / FNOMesh3D / FNOPointCloud2D) map "
+                                      f"to the fused flat optimiser kernel, got {opt}")
         routine_kwargs["optimizer"] = dict(opt.kwargs)
         if opt.func.name == "torch.optim.Adam":
             routine_kwargs["optimizer_type"] = "adam"
@@ -177,7 +178,7 @@ def build_routine(cfg: Dict[str, Any]):
         s = sch["scheduler"] if isinstance(sch, dict) else sch
         ok = ("CosineWithWarmupScheduler",) + (("StepLR",) if baseline else ())
         if not isinstance(s, Partial) or not s.func.name.endswith(ok):
-            raise NotImplementedError(f"only CosineWithWarmupScheduler (and StepLR for the FNOZongyi2DBlock / FNOMesh2D baselines) are folded into "
+            raise NotImplementedError(f"only CosineWithWarmupScheduler (and StepLR for the FNOZongyi2DBlock / FNOMesh / FNOPointCloud2D baselines) are folded into "
                                       f"the fused optimiser step, got {s}")
         routine_kwargs["scheduler"] = dict(s.kwargs)
     node = dict(r)

@@ -8,6 +8,10 @@
 // the 32-channel tiles of the spectral kernels (pad channels are exact zeros end to end), so every routine here takes a
 // leading dimension next to the logical width.  All of this is a few FLOPs per byte: plain VALU code on LDS tiles of 64
 // points, one fused pass per layer (bias, residual add, ReLU and the ReLU mask of the backward pass are folded in).
+//
+// The ffno_plin_pos_* entries are the same kernels for the pointwise stage of a geo-FNO point-cloud layer (reference
+// fourierflow/modules/zongyi_fno/point_cloud_2d.py:221-232: uc = gelu(convs[i](uc) + ws[i-1](uc) + bs[i](grid))): the points are the
+// pixels of the latent grid and the affine grid term bs[i](grid) is evaluated here from two coordinate tables.
 #include "ffno_device.h"
 #include "ffno.h"
 
@@ -34,18 +38,38 @@ static constexpr int kPlinMaxJ = 5;     // (output group, input column) items pe
 // optional second output out2 = out + res (the block-level residual x + layer(x), which must not disturb the ReLU mask)
 // VEC (ldo % 4 == 0): a thread owns four consecutive outputs of a point -- one LDS read of x[p][i] and one 16-byte read of
 // the transposed weights per four FMAs (the scalar form spends two LDS reads per FMA and is LDS-bound).
-template <bool VEC>
+// POS (ffno_plin_pos_fwd): the points are the pixels of a [B][s1][s2] grid and pre gains gw[o][0] tx[ix] + gw[o][1] ty[iy],
+// added after `add` (with gw = 0 pre keeps the bits the plain kernel computes).  Cin may be 0 there.
+struct plin_pos {
+    const float* gw;      // [Cout][2]
+    const float* tx;      // [s1]
+    const float* ty;      // [s2]
+    int s1, s2;
+};
+
+// pre + gw0 gx + gw1 gy; a zero term leaves pre's bits alone (-0 + 0 would flip the sign of a zero)
+__device__ __forceinline__ float plin_add_pos(float pre, float gw0, float gw1, float gx, float gy) {
+    const float ps = fmaf(gw1, gy, gw0 * gx);
+    return ps != 0.f ? pre + ps : pre;
+}
+
+template <bool VEC, bool POS>
 __global__ __launch_bounds__(256) void plin_fwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ W,
                                                        const float* __restrict__ b, const float* __restrict__ add,
                                                        float* __restrict__ out, int ldo, const float* __restrict__ res,
                                                        float* __restrict__ out2, float* __restrict__ pre_out, long P,
-                                                       int Cin, int Cout, int act_mode) {
+                                                       int Cin, int Cout, int act_mode, plin_pos pos) {
     FFNO_DYN_SMEM(smem);
     const int t = threadIdx.x, sx = Cin + 1;
     const int cp = VEC ? (Cout + 3) / 4 * 4 : Cout;       // VEC: weights transposed to [Cin][cp], zero-padded columns
     float* xs = reinterpret_cast<float*>(smem);          // [tile][Cin + 1]
     float* ws = xs + (kPlinTile * sx + 3) / 4 * 4;       // VEC: [Cin][cp]   scalar: [Cout][Cin + 1]
     float* bs = ws + (VEC ? Cin * cp : Cout * sx);       // [cp]
+    float* gws = bs + (Cout + 3) / 4 * 4;                // POS: [Cout][2], then the tile's gx[tile], gy[tile]
+    float* gxs = gws + 2 * Cout;
+    float* gys = gxs + kPlinTile;
+    if (POS)
+        for (int e = t; e < 2 * Cout; e += 256) gws[e] = pos.gw[e];
     if (VEC) {
         for (int e = t; e < Cin * cp; e += 256) {
             const int i = e / cp, o = e - i * cp;
@@ -65,6 +89,12 @@ __global__ __launch_bounds__(256) void plin_fwd_kernel(const float* __restrict__
             const int p = e / Cin, i = e - p * Cin;
             xs[p * sx + i] = x[(p0 + p) * ldx + i];
         }
+        if (POS)
+            for (int p = t; p < np; p += 256) {
+                const long q = (p0 + p) % ((long)pos.s1 * pos.s2);
+                gxs[p] = pos.tx[q / pos.s2];
+                gys[p] = pos.ty[q % pos.s2];
+            }
         __syncthreads();
         if (VEC) {
             const int l4 = ldo / 4;
@@ -91,6 +121,7 @@ __global__ __launch_bounds__(256) void plin_fwd_kernel(const float* __restrict__
                     const bool live = o + u < Cout;
                     float a = live ? v[u] : 0.f;
                     if (live && add) a += add[idx + u];
+                    if (POS && live) a = plin_add_pos(a, gws[2 * (o + u)], gws[2 * (o + u) + 1], gxs[p], gys[p]);
                     prev[u] = a;
                     outv[u] = live ? plin_act(a, act_mode) : 0.f;
                 }
@@ -111,6 +142,7 @@ __global__ __launch_bounds__(256) void plin_fwd_kernel(const float* __restrict__
                     const float* xr = xs + p * sx;
                     for (int i = 0; i < Cin; ++i) v = fmaf(wr[i], xr[i], v);
                     if (add) v += add[(p0 + p) * ldo + o];
+                    if (POS) v = plin_add_pos(v, gws[2 * o], gws[2 * o + 1], gxs[p], gys[p]);
                     if (pre_out) pre_out[(p0 + p) * ldo + o] = v;
                     v = plin_act(v, act_mode);
                 } else if (pre_out) {
@@ -195,19 +227,24 @@ __global__ __launch_bounds__(256) void plin_bwd_data_kernel(const float* __restr
 // part[s][o][i] = sum over the points of slice s of dpre[p][o] * x[p][i],  i = Cin is the bias column (x = 1).
 // A thread owns one input column i and kPlinOB consecutive outputs: per point one LDS read of x and kPlinOB / 4 vector
 // reads of dpre (a broadcast: the lanes of a wave share o) feed kPlinOB FMAs.
+// POS (ffno_plin_pos_bwd_weights): two more columns, i = Cin + 1 with x = tx[ix] and i = Cin + 2 with x = ty[iy] (the gradient of
+// gw); MAXJ covers the two extra columns of every output group.  dpre_out (optional, layout of g) receives dpre: each point
+// belongs to one slice, so it is written once.
+template <int MAXJ, bool POS>
 __global__ __launch_bounds__(256) void plin_wgrad_partial_kernel(const float* __restrict__ g, int ldg,
                                                                  const float* __restrict__ act, const float* __restrict__ x,
                                                                  int ldx, float* __restrict__ part, long P, int Cin, int Cout,
-                                                                 long per, int act_mode) {
+                                                                 long per, int act_mode, plin_pos pos,
+                                                                 float* __restrict__ dpre_out) {
     FFNO_DYN_SMEM(smem);
-    const int t = threadIdx.x, sx = Cin + 1, npairs = Cout * sx;
+    const int t = threadIdx.x, sx = Cin + (POS ? 3 : 1), npairs = Cout * sx;
     const int sdp = (Cout + kPlinOB - 1) / kPlinOB * kPlinOB;       // dpre row, padded with zeros to whole output groups
     float* ds = reinterpret_cast<float*>(smem);          // [tile][sdp]
     float* xs = ds + kPlinTile * sdp;                    // [tile][Cin + 1]
     const int nog = sdp / kPlinOB, nitems = sx * nog;    // item = (output group, input column), column fastest
-    float acc[kPlinMaxJ][kPlinOB];
+    float acc[MAXJ][kPlinOB];
     FFNO_UNROLL
-    for (int j = 0; j < kPlinMaxJ; ++j) {
+    for (int j = 0; j < MAXJ; ++j) {
         FFNO_UNROLL
         for (int u = 0; u < kPlinOB; ++u) acc[j][u] = 0.f;
     }
@@ -226,13 +263,31 @@ __global__ __launch_bounds__(256) void plin_wgrad_partial_kernel(const float* __
             }
             ds[e] = v;
         }
+        if (POS && dpre_out)
+            for (int e = t; e < np * ldg; e += 256) {
+                const int p = e / ldg, o = e - p * ldg;
+                float v = 0.f;
+                if (o < Cout) {
+                    const long idx = (p0 + p) * ldg + o;
+                    v = g[idx];
+                    if (act) v *= plin_dact(act[idx], act_mode);
+                }
+                dpre_out[(p0 + p) * ldg + o] = v;
+            }
         for (int e = t; e < np * sx; e += 256) {
             const int p = e / sx, i = e - p * sx;
-            xs[e] = i < Cin ? x[(p0 + p) * ldx + i] : 1.f;
+            float v = 1.f;
+            if (i < Cin) {
+                v = x[(p0 + p) * ldx + i];
+            } else if (POS && i > Cin) {
+                const long q = (p0 + p) % ((long)pos.s1 * pos.s2);
+                v = i == Cin + 1 ? pos.tx[q / pos.s2] : pos.ty[q % pos.s2];
+            }
+            xs[e] = v;
         }
         __syncthreads();
         FFNO_UNROLL
-        for (int j = 0; j < kPlinMaxJ; ++j) {
+        for (int j = 0; j < MAXJ; ++j) {
             const int item = t + 256 * j;
             if (item < nitems) {
                 const int og = item / sx, i = item - og * sx;
@@ -253,7 +308,7 @@ __global__ __launch_bounds__(256) void plin_wgrad_partial_kernel(const float* __
         }
     }
     FFNO_UNROLL
-    for (int j = 0; j < kPlinMaxJ; ++j) {
+    for (int j = 0; j < MAXJ; ++j) {
         const int item = t + 256 * j;
         if (item < nitems) {
             const int og = item / sx, i = item - og * sx;
@@ -267,10 +322,11 @@ __global__ __launch_bounds__(256) void plin_wgrad_partial_kernel(const float* __
 }
 
 // dW[o][i] (+)= sum_s part[s][o][i]: one 64-lane wave per (o, i) pair, the slices spread over the lanes
+// dgw != nullptr: rows of Cin + 3 columns, the last two go to dgw[o][0..1]
 __global__ __launch_bounds__(256) void plin_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ dW,
-                                                                float* __restrict__ db, int Cin, int Cout, int nsplit,
-                                                                int accumulate) {
-    const int sx = Cin + 1, npairs = Cout * sx;
+                                                                float* __restrict__ db, float* __restrict__ dgw, int Cin,
+                                                                int Cout, int nsplit, int accumulate) {
+    const int sx = Cin + (dgw ? 3 : 1), npairs = Cout * sx;
     __shared__ float red[256];
     // block = 4 pairs x 64 slices-lanes; consecutive threads take consecutive pairs so the loads stay coalesced
     const int q = blockIdx.x * 4 + (threadIdx.x & 3);
@@ -286,7 +342,7 @@ __global__ __launch_bounds__(256) void plin_wgrad_reduce_kernel(const float* __r
     }
     if (threadIdx.x < 4 && q < npairs) {
         const int o = q / sx, i = q - o * sx;
-        float* dst = i < Cin ? dW + o * Cin + i : (db ? db + o : nullptr);
+        float* dst = i < Cin ? dW + o * Cin + i : (i == Cin ? (db ? db + o : nullptr) : dgw + 2 * o + (i - Cin - 1));
         if (dst) *dst = accumulate ? *dst + red[threadIdx.x] : red[threadIdx.x];
     }
 }
@@ -339,11 +395,42 @@ int ffno_plin_fwd(const float* x, int ldx, const float* W, const float* b, const
     const size_t xsz = ((size_t)kPlinTile * (Cin + 1) + 3) / 4 * 4;
     const size_t lds = sizeof(float) * (xsz + (vec ? (size_t)Cin * cp + cp : (size_t)Cout * (Cin + 1) + Cout));
     if (vec)
-        FFNO_LAUNCH(plin_fwd_kernel<true>, dim3(plin_grid(P)), dim3(256), lds, (hipStream_t)stream, x, ldx, W, b, add, out, ldo,
-                    res, out2, pre_out, P, Cin, Cout, act_mode);
+        FFNO_LAUNCH((plin_fwd_kernel<true, false>), dim3(plin_grid(P)), dim3(256), lds, (hipStream_t)stream, x, ldx, W, b, add, out,
+                    ldo, res, out2, pre_out, P, Cin, Cout, act_mode, plin_pos{});
     else
-        FFNO_LAUNCH(plin_fwd_kernel<false>, dim3(plin_grid(P)), dim3(256), lds, (hipStream_t)stream, x, ldx, W, b, add, out, ldo,
-                    res, out2, pre_out, P, Cin, Cout, act_mode);
+        FFNO_LAUNCH((plin_fwd_kernel<false, false>), dim3(plin_grid(P)), dim3(256), lds, (hipStream_t)stream, x, ldx, W, b, add, out,
+                    ldo, res, out2, pre_out, P, Cin, Cout, act_mode, plin_pos{});
+    return plin_status();
+}
+
+// the linear term is optional in the position-aware stage (x = W = NULL: Cin counts as 0); the width limits are those of
+// ffno_plin_* (the weight-gradient kernel takes its two extra columns from a larger MAXJ, not from a tighter limit)
+static inline bool plin_pos_args_ok(const float* x, const float* W, const float* tx, const float* ty, int B, int s1, int s2,
+                                    int ld_in, int Cin) {
+    return (!x) == (!W) && tx && ty && B >= 1 && s1 >= 1 && s2 >= 1 && (x ? (Cin >= 1 && ld_in >= Cin) : true);
+}
+
+int ffno_plin_pos_fwd(const float* x, int ldx, const float* W, const float* b, const float* add, const float* gw, const float* tx,
+                      const float* ty, float* out, int ldo, float* pre_out, int B, int s1, int s2, int Cin, int Cout,
+                      int act_mode, void* stream) {
+    if (!gw || !out || !plin_pos_args_ok(x, W, tx, ty, B, s1, s2, ldx, Cin) || ldo < Cout || act_mode < 0 || act_mode > 2)
+        return FFNO_EINVAL;
+    if (!ffno_plin_supported(x ? Cin : 1, Cout)) return FFNO_EUNSUPPORTED;
+    if (!x) Cin = 0;
+    const long P = (long)B * s1 * s2;
+    const bool vec = ldo % 4 == 0 && ((uintptr_t)out % 16 == 0) && (!add || (uintptr_t)add % 16 == 0) &&
+                     (!pre_out || (uintptr_t)pre_out % 16 == 0);
+    const int cp = (Cout + 3) / 4 * 4;
+    const size_t xsz = ((size_t)kPlinTile * (Cin + 1) + 3) / 4 * 4;
+    const size_t lds = sizeof(float) * (xsz + (vec ? (size_t)Cin * cp : (size_t)Cout * (Cin + 1)) + cp + 2 * (size_t)Cout +
+                                        2 * kPlinTile);
+    const plin_pos pos{gw, tx, ty, s1, s2};
+    if (vec)
+        FFNO_LAUNCH((plin_fwd_kernel<true, true>), dim3(plin_grid(P)), dim3(256), lds, (hipStream_t)stream, x, ldx, W, b, add, out,
+                    ldo, nullptr, nullptr, pre_out, P, Cin, Cout, act_mode, pos);
+    else
+        FFNO_LAUNCH((plin_fwd_kernel<false, true>), dim3(plin_grid(P)), dim3(256), lds, (hipStream_t)stream, x, ldx, W, b, add, out,
+                    ldo, nullptr, nullptr, pre_out, P, Cin, Cout, act_mode, pos);
     return plin_status();
 }
 
@@ -379,12 +466,35 @@ int ffno_plin_bwd_weights(const float* g, int ldg, const float* act, const float
     const long per = ((P + nsplit - 1) / nsplit + kPlinTile - 1) / kPlinTile * kPlinTile;
     const int sdp = (Cout + kPlinOB - 1) / kPlinOB * kPlinOB;
     const size_t lds = sizeof(float) * ((size_t)kPlinTile * sdp + (size_t)kPlinTile * (Cin + 1));
-    FFNO_LAUNCH(plin_wgrad_partial_kernel, dim3(nsplit), dim3(256), lds, (hipStream_t)stream, g, ldg, act, x, ldx, part, P, Cin,
-                Cout, per, act_mode);
+    FFNO_LAUNCH((plin_wgrad_partial_kernel<kPlinMaxJ, false>), dim3(nsplit), dim3(256), lds, (hipStream_t)stream, g, ldg, act, x,
+                ldx, part, P, Cin, Cout, per, act_mode, plin_pos{}, nullptr);
     int rc = plin_status();
     if (rc) return rc;
     const int npairs = Cout * (Cin + 1);
-    FFNO_LAUNCH(plin_wgrad_reduce_kernel, dim3((npairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, part, dW, db, Cin, Cout,
+    FFNO_LAUNCH(plin_wgrad_reduce_kernel, dim3((npairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, part, dW, db, nullptr, Cin,
+                Cout, nsplit, accumulate);
+    return plin_status();
+}
+
+int ffno_plin_pos_bwd_weights(const float* g, int ldg, const float* act, const float* x, int ldx, const float* tx, const float* ty,
+                              float* part, float* dW, float* db, float* dgw, float* dpre_out, int B, int s1, int s2, int Cin,
+                              int Cout, int accumulate, int act_mode, void* stream) {
+    if (!g || !part || !dgw || !plin_pos_args_ok(x, dW, tx, ty, B, s1, s2, ldx, Cin) || ldg < Cout || act_mode < 0 ||
+        act_mode > 2)
+        return FFNO_EINVAL;
+    if (!ffno_plin_supported(x ? Cin : 1, Cout)) return FFNO_EUNSUPPORTED;
+    if (!x) Cin = 0;
+    const long P = (long)B * s1 * s2;
+    const int nsplit = ffno_plin_wgrad_nsplit(P);
+    const long per = ((P + nsplit - 1) / nsplit + kPlinTile - 1) / kPlinTile * kPlinTile;
+    const int sdp = (Cout + kPlinOB - 1) / kPlinOB * kPlinOB;
+    const size_t lds = sizeof(float) * ((size_t)kPlinTile * sdp + (size_t)kPlinTile * (Cin + 3));
+    FFNO_LAUNCH((plin_wgrad_partial_kernel<kPlinMaxJ + 1, true>), dim3(nsplit), dim3(256), lds, (hipStream_t)stream, g, ldg, act,
+                x, ldx, part, P, Cin, Cout, per, act_mode, plin_pos{nullptr, tx, ty, s1, s2}, dpre_out);
+    int rc = plin_status();
+    if (rc) return rc;
+    const int npairs = Cout * (Cin + 3);
+    FFNO_LAUNCH(plin_wgrad_reduce_kernel, dim3((npairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, part, dW, db, dgw, Cin, Cout,
                 nsplit, accumulate);
     return plin_status();
 }

@@ -6,4 +6,4 @@ from .iphi import IPhi  # noqa: F401
 from .linear import WNLinear  # noqa: F401
 from .normalizer import Normalizer  # noqa: F401
 from .position import fourier_encode  # noqa: F401
-from .zongyi_fno import FNOMesh2D, FNOMesh3D, FNOPlus2DBlock, FNOZongyi2DBlock  # noqa: F401
+from .zongyi_fno import FNOMesh2D, FNOMesh3D, FNOPlus2DBlock, FNOPointCloud2D, FNOZongyi2DBlock  # noqa: F401

@@ -38,6 +38,9 @@ class SpectralConv2d(_ComplexCornerWeights):
 
 
 class FNOFactorizedPointCloud2D(nn.Module):
+    # registered parameters that forward never reads (PointCloudExperiment keeps those out of the optimiser)
+    unused_parameter_prefixes = ("ws.",)
+
     def __init__(self, modes1, modes2, width, in_channels, out_channels, n_layers=4, is_mesh=True, s1=40, s2=40,
                  share_weight=False):
         super().__init__()

@@ -529,6 +529,129 @@ def grid_to_mixed_corners(x, weights1, weights2):
     return torch.view_as_complex(_points_major(grid_to_mixed_modes(x, w1, w2)).contiguous())
 
 
+class _MixCornerModesFn(torch.autograd.Function):
+    """Mode-major corners z [m2, 2 m1, B, 2, C] mixed with the two corner weight tensors ([C, C, m1, m2, 2] each,
+    `bixy,ioxy->boxy`): the launches _GridToMixedModesFn runs after its analysis, on a spectrum the caller already has."""
+
+    @staticmethod
+    def forward(ctx, z, w1, w2, grid):
+        lib = _lib.get_lib()
+        m2, R, B, _, C = z.shape
+        m1 = R // 2
+        ctx.chain = ch = _chain(B, grid, (m1, m2), C, z.device, _lib.is_test_backend())
+        st = _lib.current_stream(z.device)
+        f32 = dict(dtype=torch.float32, device=z.device)
+        wp, wpt = torch.empty(ch.planes_floats, **f32), torch.empty(ch.planes_floats, **f32)
+        _capi.check(lib.ffno_fw2d_pack2(_p(w1), _p(w2), _p(wp), _p(wpt), C, m1, m2, st), "fw2d_pack2")
+        out = torch.empty_like(z)
+        ch.mix(z, wp, out, True, st)
+        ctx.save_for_backward(z, wpt)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.get_lib()
+        z, wpt = ctx.saved_tensors
+        ch = ctx.chain
+        (m1, m2), C = ch.Ks, ch.C
+        st = _lib.current_stream(g.device)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        g = g.contiguous()
+        dz = None
+        if ctx.needs_input_grad[0]:
+            dz = torch.empty_like(z)
+            ch.mix(g, wpt, dz, False, st)
+        part = torch.empty(ch.planes_floats, **f32)
+        gw1, gw2 = torch.empty(C, C, m1, m2, 2, **f32), torch.empty(C, C, m1, m2, 2, **f32)
+        ch.fw_grad_partial(z, g, part, st)
+        _capi.check(lib.ffno_fw2d_grad_reduce2(_p(part), _p(gw1), _p(gw2), C, m1, m2, 1, 0, st), "fw2d_grad_reduce2")
+        return dz, gw1, gw2, None
+
+
+def mix_corner_modes(z, w1, w2, grid=None):
+    """The corner mix of the point-cloud SpectralConv2d on a spectrum that is already in mode space (reference
+    zongyi_fno/point_cloud_2d.py:56-59 after fft2d): z [m2, 2 m1, B, 2, C] mode-major corners, rows kx' < m1 x w1 and rows
+    kx' >= m1 x w2 (`bixy,ioxy->boxy`; real views [C, C, m1, m2, 2]) -> the same layout.  Differentiable in z and both weights.
+    ``grid`` = (s1, s2) of the latent grid the spectrum goes to: the op then shares the chain of the neighbouring
+    modes_to_grid / grid_to_mixed_modes (the mix itself does not depend on it)."""
+    _lib.require_device_tensor(z, "corner modes")
+    if z.dim() != 5 or z.shape[1] % 2 or z.shape[3] != 2:
+        raise ValueError(f"expected mode-major corners [m2, 2 m1, B, 2, C], got {tuple(z.shape)}")
+    m2, m1, C = z.shape[0], z.shape[1] // 2, z.shape[4]
+    if w1.shape != w2.shape or tuple(w1.shape) != (C, C, m1, m2, 2):
+        raise ValueError(f"expected two weights [{C}, {C}, {m1}, {m2}, 2], got {tuple(w1.shape)}, {tuple(w2.shape)}")
+    grid = (int(grid[0]), int(grid[1])) if grid is not None else (2 * m1, 2 * max(m1, m2))
+    _corner_guard(m1, m2, grid[0], grid[1], C)
+    return _MixCornerModesFn.apply(z.contiguous(), w1.contiguous(), w2.contiguous(), grid)
+
+
+# ---- the pointwise stage of a geo-FNO layer on the latent grid (csrc/plin.hip: ffno_plin_pos_*) --------------------------------
+_GRID_TABLES = {}
+
+
+def _grid_tables(s1, s2, device):
+    """tx[s1], ty[s2]: the reference's grid coordinates, float32(np.linspace(0, 1, s)) (point_cloud_2d.py:245-253)."""
+    key = (s1, s2, str(device))
+    if key not in _GRID_TABLES:
+        _GRID_TABLES[key] = tuple(torch.tensor(np.linspace(0, 1, s), dtype=torch.float).to(device) for s in (s1, s2))
+    return _GRID_TABLES[key]
+
+
+class _GeoFNOPointwiseFn(torch.autograd.Function):
+    """gelu(W x + add + gw . grid + b1 [+ b2]) over a [B, s1, s2, C] grid; x = W = b2 = None: no 1x1 convolution (layer 0)."""
+
+    @staticmethod
+    def forward(ctx, add, gw, b1, x, W, b2):
+        lib = _lib.get_lib()
+        B, s1, s2, C = add.shape
+        st = _lib.current_stream(add.device)
+        tx, ty = _grid_tables(s1, s2, add.device)
+        b = b1 if b2 is None else b1 + b2
+        out, pre = torch.empty_like(add), torch.empty_like(add)
+        _capi.check(lib.ffno_plin_pos_fwd(_p(x), C, _p(W), _p(b), _p(add), _p(gw), _p(tx), _p(ty), _p(out), C, _p(pre), B, s1, s2, C,
+                                          C, 2, st), "plin_pos_fwd")
+        ctx.save_for_backward(pre, x, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pre, x, W = ctx.saved_tensors
+        lib = _lib.get_lib()
+        B, s1, s2, C = pre.shape
+        P = B * s1 * s2
+        st = _lib.current_stream(g.device)
+        tx, ty = _grid_tables(s1, s2, g.device)
+        g = g.contiguous()
+        f32 = dict(dtype=torch.float32, device=g.device)
+        dpre, dx, dW = torch.empty_like(pre), None, None
+        if x is not None:
+            dx, dW = torch.empty_like(x), torch.empty_like(W)
+            _capi.check(lib.ffno_plin_bwd_data(_p(g), C, _p(pre), _p(W), _p(dx), C, _p(dpre), P, C, C, 0, 2, st), "plin_bwd_data")
+        part = torch.empty(int(lib.ffno_plin_wgrad_nsplit(P)) * C * (C + 3), **f32)
+        db, dgw = torch.empty(C, **f32), torch.empty(C, 2, **f32)
+        _capi.check(lib.ffno_plin_pos_bwd_weights(_p(g), C, _p(pre), _p(x), C, _p(tx), _p(ty), _p(part), _p(dW), _p(db), _p(dgw),
+                                                  None if x is not None else _p(dpre), B, s1, s2, C, C, 0, 2, st),
+                    "plin_pos_bwd_weights")
+        return dpre, dgw, db, dx, dW, (db if x is not None else None)
+
+
+def geofno_pointwise(add, bs, x=None, ws=None):
+    """The pointwise stage of a geo-FNO layer (reference zongyi_fno/point_cloud_2d.py:222-224 and :229-232):
+    ``gelu(add + ws(x) + bs(grid))`` on channels-last grids [B, s1, s2, W]; ``add`` the spectral branch, bs = nn.Conv2d(2, W, 1)
+    on the [0, 1]^2 coordinates of the pixels, ws = nn.Conv2d(W, W, 1) on x (both None: layer 0).  The grid term is evaluated
+    inside the kernel from the two coordinate tables."""
+    _lib.require_device_tensor(add, "spectral branch")
+    if add.dim() != 4 or (x is None) != (ws is None) or (x is not None and x.shape != add.shape):
+        raise ValueError(f"expected add [B, s1, s2, W] and x of the same shape with ws, got {tuple(add.shape)}")
+    C = add.shape[3]
+    if not _lib.get_lib().ffno_plin_supported(C, C):
+        raise ValueError(f"width {C} is outside the pointwise-linear kernel set")
+    if x is None:
+        return _GeoFNOPointwiseFn.apply(add.contiguous(), bs.weight.reshape(C, 2).contiguous(), bs.bias, None, None, None)
+    return _GeoFNOPointwiseFn.apply(add.contiguous(), bs.weight.reshape(C, 2).contiguous(), bs.bias, x.contiguous(),
+                                    ws.weight.reshape(C, C).contiguous(), ws.bias)
+
+
 # ---- the two per-point networks of the elasticity F-FNO ---------------------------------------------------------------------
 def _param_struct(cls, tensors):
     return cls(*[t.data_ptr() for t in tensors])

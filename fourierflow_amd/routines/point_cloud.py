@@ -1,14 +1,18 @@
 """PointCloudExperiment -- counterpart of ``fourierflow.routines.PointCloudExperiment`` (reference routines/point_cloud.py:9-65):
-the elasticity F-FNO (``FNOFactorizedPointCloud2D`` + ``IPhi``) regressing the stress ``sigma`` at the mesh points ``xy`` from the
-geometry code ``rr`` under the relative-L2 loss, with the manual optimisation step of routines/base.py:27-52.
+the elasticity F-FNO (``FNOFactorizedPointCloud2D`` + ``IPhi``) or its geo-FNO baseline (``FNOPointCloud2D`` + ``IPhi``)
+regressing the stress ``sigma`` at the mesh points ``xy`` from the geometry code ``rr`` under the relative-L2 loss, with the
+manual optimisation step of routines/base.py:27-52.
 
 The reference adds ``0 * loss_reg`` (IPhi on ``N`` random points against the identity, point_cloud.py:36-39): multiplied by zero
 it contributes no gradient, so it is not evaluated here; ``N`` is kept as an attribute.  Validation and test use the same loss.
 
 The optimiser step is the project's: every parameter that receives a gradient is a view into one flat fp32 buffer, one
-``ffno_adamw_flat`` launch per step, the cosine-with-warm-up schedule of :class:`FFNOTrainer`.  torch.optim.AdamW skips
-parameters whose ``.grad`` is None (weight decay included), so ``model.ws.*`` and ``iphi.fc_no_code.*`` -- registered, never
-used -- stay out of the flat buffer and are never written.  Shared Fourier weights appear once.
+``ffno_adamw_flat`` launch per step under the cosine-with-warm-up schedule of :class:`FFNOTrainer` (the F-FNO configs), or
+``optimizer_type="adam"``: one ``ffno_adam_flat`` launch (torch.optim.Adam, L2 weight decay) under StepLR(step_size, gamma)
+per EPOCH, recognised by its keyword arguments (the geo-FNO configs), exactly as StructuredMeshExperiment does.
+torch.optim.Adam(W) skips parameters whose ``.grad`` is None (weight decay included), so what is registered and never used stays
+out of the flat buffer and is never written: ``iphi.fc_no_code.*`` always, and the prefixes a model lists in its
+``unused_parameter_prefixes`` (``ws.`` of the F-FNO; the geo-FNO uses its ``ws``).  Shared Fourier weights appear once.
 """
 from typing import Optional
 
@@ -64,8 +68,9 @@ class _TrainedParameters:
 
     def __init__(self, routine):
         seen, named = set(), []
+        skip = tuple("model." + pre for pre in getattr(routine.model, "unused_parameter_prefixes", ())) + ("iphi.fc_no_code.",)
         for n, p in routine.named_parameters():      # (shared tensors are reported once)
-            if n.startswith("model.ws.") or n.startswith("iphi.fc_no_code.") or id(p) in seen:
+            if n.startswith(skip) or id(p) in seen:
                 continue
             seen.add(id(p))
             named.append((n, p))
@@ -81,20 +86,37 @@ class _TrainedParameters:
 
 class PointCloudExperiment(CheckpointMixin, nn.Module):
     def __init__(self, model: nn.Module, iphi: nn.Module, N: int = 1000, optimizer: Optional[dict] = None,
-                 scheduler: Optional[dict] = None, **unused):
+                 scheduler: Optional[dict] = None, optimizer_type: str = "adamw", **unused):
         super().__init__()
         reject_unsupported_routine_kwargs(unused)
-        self.model, self.iphi, self.N = model, iphi, N
+        if optimizer_type not in ("adamw", "adam"):
+            raise NotImplementedError(f"optimizer_type={optimizer_type!r}: the fused step implements AdamW and Adam")
+        self.model, self.iphi, self.N, self.optimizer_type = model, iphi, N, optimizer_type
         self._opt_kw = dict(lr=1e-3, weight_decay=1e-4)
         self._opt_kw.update(optimizer or {})
-        self._sch_kw = dict(num_warmup_steps=500, num_training_steps=10000, num_cycles=0.5)
+        # the F-FNO configs run cosine-with-warm-up per step, the geo-FNO baseline (FNOPointCloud2D) torch.optim.Adam +
+        # StepLR(step_size, gamma) per EPOCH -- recognised by its keyword arguments
+        self._step_lr = scheduler is not None and "step_size" in scheduler
+        self._sch_kw = dict(step_size=50, gamma=0.5) if self._step_lr else \
+            dict(num_warmup_steps=500, num_training_steps=10000, num_cycles=0.5)
         self._sch_kw.update(scheduler or {})
+        self.current_epoch = 0
         self._trainer: Optional[FFNOTrainer] = None
 
     def trainer(self) -> FFNOTrainer:
         if self._trainer is None:
-            self._trainer = FFNOTrainer(_TrainedParameters(self), **self._opt_kw, **self._sch_kw)
+            kw = dict(decoupled=self.optimizer_type == "adamw", **self._opt_kw)
+            if self._step_lr:
+                tr = FFNOTrainer(_TrainedParameters(self), **kw)
+                step, gamma = int(self._sch_kw["step_size"]), float(self._sch_kw["gamma"])
+                tr.lr_factor = lambda: gamma ** (self.current_epoch // step)
+                self._trainer = tr
+            else:
+                self._trainer = FFNOTrainer(_TrainedParameters(self), **kw, **self._sch_kw)
         return self._trainer
+
+    def on_train_epoch_end(self):
+        self.current_epoch += 1
 
     def forward(self, batch):
         return self.model(batch['xy'], code=batch['rr'], iphi=self.iphi)

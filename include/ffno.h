@@ -82,7 +82,7 @@ const char* ffno_build_target(void);
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
  * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
  * in the same way. */
-#define FFNO_ABI_VERSION 10
+#define FFNO_ABI_VERSION 11
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -1083,6 +1083,28 @@ size_t ffno_plin_wgrad_partial_floats(long P, int Cin, int Cout);
 int ffno_plin_bwd_weights(const float* g, int ldg, const float* act, const float* x, int ldx, float* part,
                           float* dW, float* db, long P, int Cin, int Cout, int accumulate, int act_mode,
                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The pointwise stage of a geo-FNO layer on its latent grid (zongyi_fno/point_cloud_2d.py:221-224 layer 0, :227-232 the middle
+ * layers:  uc = gelu(convs[i](uc) + ws[i-1](uc) + bs[i](grid))): the 1x1 convolution of ffno_plin_fwd whose points are the
+ * pixels p = (sample, ix, iy) of a [B][s1][s2] grid, with the affine grid term bs[i](grid) folded in -- no [s1 s2, W] image, no
+ * broadcast add, no batch reduction of its gradient:
+ *   pos_fwd:          pre = b[o] + sum_i W[o][i] x[p][i] + add[p][o] + gw[o][0] tx[ix] + gw[o][1] ty[iy];  out = act(pre),
+ *                     pre_out (optional) = pre.  gw is [Cout][2] (bs[i].weight), tx[s1] / ty[s2] the grid coordinates (get_grid,
+ *                     :245-253: float32(linspace(0, 1, s))), b the caller's sum ws[i-1].bias + bs[i].bias, add the spectral branch.
+ *                     With gw = 0 the result is ffno_plin_fwd's bit for bit.
+ *   pos_bwd_weights:  dW, db as ffno_plin_bwd_weights, plus dgw[o][0] (+)= sum_p dpre[p][o] tx[ix], dgw[o][1] (+)= sum_p dpre[p][o]
+ *                     ty[iy]; deterministic two-stage reduction through `part`, ffno_plin_wgrad_nsplit(B s1 s2) * Cout * (Cin + 3)
+ *                     floats.  dpre_out (optional, layout of g) receives dpre = g * act'(.), the gradient of `add`.
+ * The data gradient is ffno_plin_bwd_data.  Leading dimensions, pad channels, act_mode and the Cin / Cout limits are those of
+ * ffno_plin_*.  Layer 0 has no 1x1 convolution: x = W (= dW) = NULL drops the linear term, Cin is then ignored.
+ * --------------------------------------------------------------------------------------------- */
+int ffno_plin_pos_fwd(const float* x, int ldx, const float* W, const float* b, const float* add, const float* gw,
+                      const float* tx, const float* ty, float* out, int ldo, float* pre_out, int B, int s1, int s2,
+                      int Cin, int Cout, int act_mode, void* stream);
+int ffno_plin_pos_bwd_weights(const float* g, int ldg, const float* act, const float* x, int ldx, const float* tx,
+                              const float* ty, float* part, float* dW, float* db, float* dgw, float* dpre_out, int B,
+                              int s1, int s2, int Cin, int Cout, int accumulate, int act_mode, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The GENERAL feed-forward path (fourierflow/modules/feedforward.py:6-24 beyond the fused kernels' n_layers = 2 / dropout = 0,
