@@ -40,9 +40,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from .markov_data import MarkovTrajectoryData, _tensor, _upload
-from .ns_data import _broadcast
-from .sample_data import DeviceSampleData, Field
+from .device_epochs import tensor, upload
+from .markov_data import MarkovTrajectoryData
+from .sample_data import DeviceSampleData, Field, broadcast
 
 
 def npz_path(path: str) -> str:
@@ -205,7 +205,7 @@ class KolmogorovBuilder:
                              f"included) and {Lc} of {Tc} of the corr trajectory: a rollout needs two and one")
         fields = [Field("data", full, (X, Y, L), X * Y, L, (X * Y * T, 0, T, k), (0, L, 1)),
                   Field("corr_data", corr, (m, m2, Lc), m * m2, Lc, (m * m2 * Tc, 0, Tc, k), (0, Lc, 1)),
-                  _broadcast("times", np.ascontiguousarray(a["time"][ds.columns(T)], dtype=np.float32))]
+                  broadcast("times", np.ascontiguousarray(a["time"][ds.columns(T)], dtype=np.float32))]
         return DeviceSampleData(fields, n, device=device, batch_size=self.batch_size, shuffle=False)
 
     def valid_data(self, device) -> DeviceSampleData:
@@ -219,4 +219,4 @@ class KolmogorovBuilder:
     def inference_data(self, device) -> Dict[str, torch.Tensor]:
         """``{'data': ...}`` on `device`: the joined test trajectories at every k-th time (``end`` is not applied: :60-68)."""
         full = self.test_dataset.arrays()["full"]
-        return {"data": _upload(_tensor(np.ascontiguousarray(full[..., ::self.test_dataset.k]), "data"), torch.device(device))}
+        return {"data": upload(tensor(np.ascontiguousarray(full[..., ::self.test_dataset.k]), "data"), torch.device(device))}

@@ -31,6 +31,7 @@ import torch
 from .. import _capi, _lib
 from ..engine import _p
 from .kolmogorov import load_initial, npz_path
+from .npz_stream import NpzStream
 
 TWO_PI = 2.0 * math.pi
 ALPHA = (0.0, 0.1496590219993, 0.3704009573644, 0.6222557631345, 0.9582821306748, 1.0)
@@ -289,17 +290,15 @@ def _outputs(stepper: KolmogorovStepper, sizes: Sequence[int]) -> Dict[int, np.n
     return {m: stepper.downsample(m, vel).cpu().numpy() for m in sizes}
 
 
-def generate_kolmogorov(plan: KolmogorovPlan, device, batch_size: int = 1, sink_factory=None) -> Dict[str, Dict[str, List[int]]]:
+def generate_kolmogorov(plan: KolmogorovPlan, device, batch_size: int = 1) -> Dict[str, Dict[str, List[int]]]:
     """Run ``plan`` and write its files, ``batch_size`` trajectories at a time (builders/kolmogorov.py:328-405 for every batch):
     with warmup_steps > 0 advance warmup_steps x inner_steps steps and write the downsampled final fields, ``vorticity``
     [n, size, size]; otherwise take outer_steps snapshots inner_steps steps apart and write, per (size, k), every k-th starting
     at the k-th as ``vorticity`` [n, outer_steps // k, size, size] with ``time`` [outer_steps // k].  Initial fields: the file
-    ``init_path`` names (its .npz sibling at the simulation size) or ``initial_vorticity``.  ``sink_factory(path, rows)`` makes the
-    streamed .npz writers (cli._NpzStream).  Returns {file: {array: shape}}."""
+    ``init_path`` names (its .npz sibling at the simulation size) or ``initial_vorticity``.  The files are written through the streamed
+    .npz writer (builders/npz_stream.py).  Returns {file: {array: shape}}."""
     if not plan.out_vorticity:
         raise _not_built("out_vorticity: false", "the files hold the vorticity; velocity outputs (vx, vy) are not written")
-    if sink_factory is None:
-        from ..cli import _NpzStream as sink_factory
     n, N = plan.n_trajectories, plan.N
     if not _lib.get_lib().ffno_kf2d_supported(N):
         raise ValueError(f"generate kolmogorov: grid size {N} is not a power of two in 16 ... 4096 (ffno_kf2d_supported)")
@@ -311,7 +310,7 @@ def generate_kolmogorov(plan: KolmogorovPlan, device, batch_size: int = 1, sink_
                              f"[{n}, {N}, {N}]")
     sizes = sorted({size for size, _ in plan.out_sizes})
     warmup = plan.warmup_steps > 0
-    sinks = {key: sink_factory(path, n) for key, path in plan.files.items()}
+    sinks = {key: NpzStream(path, n) for key, path in plan.files.items()}
     try:
         for done in range(0, n, batch_size):
             b = min(batch_size, n - done)

@@ -32,8 +32,7 @@ from typing import Dict
 import numpy as np
 
 from .markov_data import MarkovTrajectoryData
-from .ns_data import _broadcast
-from .sample_data import DeviceSampleData, Field, rows
+from .sample_data import DeviceSampleData, Field, broadcast, rows
 
 SPLITS = ("train", "valid", "test")
 
@@ -123,7 +122,7 @@ class NSContextualBuilder:
             fields.append(every_kth("f", f) if f.ndim == 4 else rows("f", f))
         if self.append_mu:
             fields.append(rows("mu", a["mu"]))
-        fields.append(_broadcast("times", self.times))
+        fields.append(broadcast("times", self.times))
         return DeviceSampleData(fields, n, device=device, batch_size=self.batch_size, shuffle=False)
 
     def valid_data(self, device) -> DeviceSampleData:

@@ -23,8 +23,9 @@ from typing import Dict
 import numpy as np
 import torch
 
-from .markov_data import MarkovTrajectoryData, _tensor, _upload
-from .sample_data import DeviceSampleData, Field, rows
+from .device_epochs import tensor, upload
+from .markov_data import MarkovTrajectoryData
+from .sample_data import DeviceSampleData, Field, broadcast, rows
 
 
 def _load_u(data_path: str) -> np.ndarray:
@@ -89,13 +90,7 @@ class _NSBuilder:
         """``{'data': u[:512]}`` on `device`: the first min(512, n) trajectories of the file AS IT IS -- the reference does not
         apply ``ssr`` here (ns_markov.py:57-59, ns_zongyi.py:66-68), and neither does this."""
         u = self.u if self.ssr == 1 else _load_u(self.data_path)
-        return {"data": _upload(_tensor(u[:512], "u"), torch.device(device))}
-
-
-def _broadcast(out: str, source: np.ndarray) -> Field:
-    """One row that every sample of the batch receives (sample stride 0): the `times` the reference's datasets attach to each item."""
-    L = int(source.size)
-    return Field(out, source, (L,), 1, L, (0, 0, 0, 1), (0, 0, 1))
+        return {"data": upload(tensor(u[:512], "u"), torch.device(device))}
 
 
 class NSMarkovBuilder(_NSBuilder):
@@ -115,7 +110,7 @@ class NSMarkovBuilder(_NSBuilder):
 
     def _eval_fields(self, u):
         T = u.shape[-1]
-        return [rows("data", u), _broadcast("times", np.arange(0, 20, dtype=np.float32)[:T])]
+        return [rows("data", u), broadcast("times", np.arange(0, 20, dtype=np.float32)[:T])]
 
 
 class NSZongyiBuilder(_NSBuilder):
@@ -147,7 +142,7 @@ class NSZongyiBuilder(_NSBuilder):
                   Field("y", u, (X, Y, S), X * Y, S, (X * Y * T, S, T, 1), (0, S, 1))]
         if self.append_pos:
             fields.append(Field("x", self.pos, (X, Y, C), X * Y, 2, (0, 0, 2, 1), (S, C, 1)))
-        return fields + [_broadcast("times", self.times)]
+        return fields + [broadcast("times", self.times)]
 
     def train_data(self, device, seed: int = 0, rank: int = 0, world: int = 1, shuffle: bool = True,
                    drop_last: bool = False) -> DeviceSampleData:

@@ -8,20 +8,18 @@ host -- stack, channel pick, repeat, permute -- happens in the copy.  An epoch i
 once as int32; each batch is ONE ``ffno_sample_gather`` launch for all fields, reading its ids through a pointer into that array:
 a step costs no host work beyond the launch.
 
-Order, drop-last and data parallel: the rules of ``MarkovTrajectoryData`` (builders/markov_data.py).  ``shuffle=False`` is file
-order; ``shuffle=True`` draws ``torch.randperm(n)`` once per epoch from a CPU ``torch.Generator`` seeded once with ``seed``;
-``drop_last=False`` keeps the short last batch; every rank draws the SAME permutation and rank r takes batches r, r + world, ...;
-trailing batches that do not fill every rank are dropped.
+Order, drop-last and data parallel: the schedule of ``DeviceEpochs`` (builders/device_epochs.py) over the ``n`` sample ids;
+``shuffle=False`` is file order.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Iterator, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _capi, _lib
-from .markov_data import _tensor, _upload
+from .device_epochs import DeviceEpochs, tensor, upload
 
 
 class Field(NamedTuple):
@@ -45,28 +43,27 @@ def rows(out: str, source, shape: Optional[Sequence[int]] = None) -> Field:
     return Field(out, source, tuple(shape if shape is not None else source.shape[1:]), 1, L, (L, 0, 0, 1), (0, 0, 1))
 
 
-class DeviceSampleData:
+def broadcast(out: str, source) -> Field:
+    """One row that every sample of the batch receives (sample stride 0): the `times` the reference's datasets attach to each item."""
+    L = int(source.size)
+    return Field(out, source, (L,), 1, L, (0, 0, 0, 1), (0, 0, 1))
+
+
+class DeviceSampleData(DeviceEpochs):
     def __init__(self, fields: Sequence[Field], n: int, *, device, batch_size: int, seed: int = 0, shuffle: bool = True,
                  drop_last: bool = False, rank: int = 0, world: int = 1):
-        if batch_size < 1:
-            raise ValueError(f"batch_size is at least 1, got {batch_size}")
-        if world < 1 or not 0 <= rank < world:
-            raise ValueError(f"rank {rank} is not one of {world} ranks")
+        super().__init__(device=device, batch_size=batch_size, seed=seed, shuffle=shuffle, drop_last=drop_last, rank=rank,
+                         world=world)
         if not 1 <= len(fields) <= _capi.GATHER_MAX_FIELDS:
             raise ValueError(f"a set has 1 to {_capi.GATHER_MAX_FIELDS} fields (one launch draws them all), got {len(fields)}")
         if not 1 <= n <= 2 ** 31 - 1:
             raise ValueError(f"a set holds 1 to 2^31 - 1 samples (int32 ids), got {n}")
-        self.device = torch.device(device)
-        if _lib.is_test_backend() != (self.device.type == "cpu"):
-            raise _lib.FFNOLibraryError(
-                f"DeviceSampleData on {self.device}: the HIP library draws batches from a set on an MI355X (cuda) device, "
-                f"the emulator backend from CPU tensors; there is no CPU path")
         self.n = int(n)
         self.fields, self.shapes, uploaded = [], {}, {}
         for f in fields:
             key = id(f.source)
             if key not in uploaded:      # a source that several fields read is uploaded once
-                uploaded[key] = _upload(_tensor(f.source, f.out), self.device)
+                uploaded[key] = upload(tensor(f.source, f.out), self.device)
             src = uploaded[key]
             size = 1
             for s in f.shape:
@@ -82,15 +79,7 @@ class DeviceSampleData:
                 raise ValueError(f"{f.out}: the field reaches float {last_src} of a source of {src.numel()} and float {last_dst} of a "
                                  f"sample of {size}")
             self.fields.append((f, src, size))
-        self.device = self.fields[0][1].device      # (with its index: what the ids of `gather` are compared with)
-        self.batch_size, self.shuffle, self.drop_last = int(batch_size), bool(shuffle), bool(drop_last)
-        self.rank, self.world = int(rank), int(world)
-        total = self.n // self.batch_size if self.drop_last else -(-self.n // self.batch_size)
-        self._batches = total // self.world * self.world      # the same number of batches on every rank
-        if self._batches == 0:
-            raise ValueError(f"{self.n} samples give {total} batches of {self.batch_size}: not one for each of {self.world} ranks")
-        self.gen = torch.Generator().manual_seed(int(seed))
-        self._ids: Optional[torch.Tensor] = None
+        self._schedule(self.n, "samples", self.fields[0][1])
         self._descs = (_capi.GatherField * len(self.fields))()
         for d, (f, src, size) in zip(self._descs, self.fields):
             d.src = src.data_ptr()
@@ -99,38 +88,12 @@ class DeviceSampleData:
             d.dst_offset, d.dst_q, d.dst_r = f.dst
             d.Q, d.R = f.Q, f.R
 
-    def __len__(self) -> int:
-        """Batches per epoch on this rank."""
-        return self._batches // self.world
-
-    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
-        while True:
-            yield from self.epoch()
-
-    def _epoch_ids(self) -> torch.Tensor:
-        if self.shuffle:
-            self._ids = torch.randperm(self.n, generator=self.gen).to(torch.int32).to(self.device)
-        elif self._ids is None:
-            self._ids = torch.arange(self.n, dtype=torch.int32).to(self.device)
-        return self._ids
-
-    def epoch(self) -> Iterator[Dict[str, torch.Tensor]]:
-        ids = self._epoch_ids()
-        for j in range(self.rank, self._batches, self.world):
-            lo = j * self.batch_size
-            yield self.gather(ids, lo, min(self.batch_size, self.n - lo))
-
-    def gather(self, ids: torch.Tensor, offset: int, B: int) -> Dict[str, torch.Tensor]:
-        """The batch of the B sample ids at ids[offset:] (a device int32 array): one launch."""
-        if ids.dtype != torch.int32 or ids.device != self.device or not ids.is_contiguous() or ids.dim() != 1:
-            raise ValueError("ids must be a contiguous 1-D int32 tensor on the set's device")
-        if B < 1 or offset < 0 or offset + B > ids.numel():
-            raise ValueError(f"ids[{offset}:{offset + B}] is outside the {ids.numel()} ids given")
+    def _gather(self, ids: ctypes.c_void_p, B: int) -> Dict[str, torch.Tensor]:
+        """The batch of B sample ids: one launch for all fields."""
         b = {name: torch.empty(B, *shape, dtype=torch.float32, device=self.device) for name, shape in self.shapes.items()}
         for d, (f, _, _) in zip(self._descs, self.fields):
             d.dst = b[f.out].data_ptr()
-        rc = _lib.get_lib().ffno_sample_gather(ctypes.cast(self._descs, ctypes.c_void_p), len(self.fields),
-                                               ctypes.c_void_p(ids.data_ptr() + 4 * offset), self.n, B,
+        rc = _lib.get_lib().ffno_sample_gather(ctypes.cast(self._descs, ctypes.c_void_p), len(self.fields), ids, self.n, B,
                                                _lib.current_stream(self.device))
         _capi.check(rc, "sample_gather")
         return b

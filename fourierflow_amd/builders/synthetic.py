@@ -12,6 +12,7 @@ five complex ones.  ``GaussianRF`` runs once per batch and stays plain torch, as
 from __future__ import annotations
 
 import math
+import os
 from enum import Enum
 
 import numpy as np
@@ -19,6 +20,7 @@ import torch
 
 from .. import _capi, _lib
 from ..engine import _p
+from .npz_stream import NpzStream
 
 
 class Force(str, Enum):
@@ -162,3 +164,61 @@ def solve_navier_stokes_2d(w0, visc, T, delta_t, record_steps, cycles=None, scal
             raise ValueError(f"solve_navier_stokes_2d: NaN in snapshot {len(snapshots) + 1} of {record_steps}")
         snapshots.append(w)
     return torch.stack(snapshots, dim=-1).cpu().numpy(), (None if f is None else f.cpu().numpy())
+
+
+def _training_pairs(u: np.ndarray):
+    """u [n, M, N, T] -> x, y [(n (T - 1)), M, N, 1]: every snapshot with its successor, sample-major -- the (b t) order in which
+    the reference's NavierStokesTrainingDataset enumerates its pairs (builders/ns_contextual.py:57-72 with k = 1)."""
+    n, M, N, T = u.shape
+    x = np.ascontiguousarray(np.moveaxis(u[..., :-1], -1, 1)).reshape(n * (T - 1), M, N, 1)
+    y = np.ascontiguousarray(np.moveaxis(u[..., 1:], -1, 1)).reshape(n * (T - 1), M, N, 1)
+    return x, y
+
+
+def generate_navier_stokes(path: str, device, *, n_train: int, n_valid: int, n_test: int, s: int, t: float, steps: int, mu: float,
+                           mu_min: float, mu_max: float, seed: int, delta: float, batch_size: int, force: Force, cycles: int,
+                           scaling: float, ssr: int, train_trajectories: bool) -> dict:
+    """The files of `generate navier-stokes` (fourierflow_amd/cli.py: the options are the command's): PATH.train.npz, PATH.valid.npz
+    and PATH.test.npz, each solved `batch_size` trajectories at a time, with a shorter last batch where that does not divide the
+    split, and written batch by batch.  `seed` seeds torch (initial vorticity) and, plus 1234, numpy (viscosity, force); the
+    order of the draws below is what a seeded run reproduces.  Returns the command's summary."""
+    torch.manual_seed(seed)
+    np.random.seed(seed + 1234)
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    field = GaussianRF(2, s, alpha=2.5, tau=7, device=device)
+    n_solver = math.ceil(t / delta)
+    times = (np.arange(1, steps + 1) * (n_solver // steps) * delta).astype(np.float32)
+    vary_mu, pairs = mu_min != mu_max, steps - 1
+    written = {}
+    for split, n in (("train", n_train), ("valid", n_valid), ("test", n_test)):
+        if n <= 0:
+            continue
+        as_pairs = split == "train" and not train_trajectories
+        rows_per_sample = pairs if as_pairs else 1      # the per-sample f and mu are repeated for every pair
+        sink = NpzStream(f"{path}.{split}.npz", n * rows_per_sample)
+        done = 0
+        while done < n:
+            b = min(batch_size, n - done)
+            # per batch, in this order: the initial vorticity from torch's generator; the viscosities, then (inside the solver)
+            # the seed of the random force from numpy's
+            with torch.no_grad():
+                w0 = field.sample(b)
+            nu = mu_min + (mu_max - mu_min) * np.random.rand(b) if vary_mu else mu
+            sol, f = solve_navier_stokes_2d(w0, nu, t, delta, steps, cycles, scaling, None, force, False)
+            sol = sol[:, ::ssr, ::ssr]
+            row = done * rows_per_sample
+            if as_pairs:
+                x, y = _training_pairs(sol)
+                sink.put("x", row, x)
+                sink.put("y", row, y)
+            else:
+                sink.put("data", row, sol)
+                sink.put("times", row, np.tile(times, (b, 1)))
+            if force == Force.random:
+                sink.put("f", row, np.repeat(f[:, ::ssr, ::ssr], rows_per_sample, axis=0))
+            if vary_mu:
+                sink.put("mu", row, np.repeat(nu, rows_per_sample))
+            done += b
+        written[split] = dict(file=sink.out, trajectories=n, **sink.close())
+    return dict(solver_steps=n_solver, delta=delta, grid=s, ssr=ssr, **written)

@@ -45,14 +45,17 @@ import json
 import math
 import time
 from pathlib import Path
-from typing import Dict, Iterator, List, Optional
+from types import SimpleNamespace
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
-from typer import Argument, Option, Typer
+from typer import Argument, BadParameter, Option, Typer
 
+from .builders.file_batches import Batches, holds_trajectories, initial_conditions, trajectory_batches
 from .builders.synthetic import Force
 from .config import build_routine, load_config
+from .routines import routine_kind
 
 app = Typer(add_completion=False, help=__doc__)
 _LAST: Dict[str, object] = {}
@@ -64,12 +67,6 @@ def _last_routine():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-def _kind(routine) -> str:
-    name = type(routine).__name__
-    return {"Grid2DMarkovExperiment": "markov", "Grid2DRolloutExperiment": "rollout",
-            "StructuredMeshExperiment": "mesh", "PointCloudExperiment": "pointcloud"}[name]
-
-
 def _device(device: Optional[str]) -> torch.device:
     return torch.device(device or "cuda:0")
 
@@ -93,97 +90,48 @@ def _init_distributed(device: Optional[str]):
     return rank, world, dev
 
 
-class _Batches:
-    """Batches of the routine's geometry: slices of an .npz file, or synthetic."""
-
-    def __init__(self, routine, cfg, dev, data: Optional[Path], batch_size: Optional[int], grid: int, size: Optional[List[int]],
-                 seed: int, rank: int = 0, world: int = 1):
-        self.routine, self.dev, self.kind = routine, dev, _kind(routine)
-        self.rank, self.world = rank, world      # data parallel: rank r takes every world-th batch of a file / its own stream
-        seed = seed + 1000003 * rank
-        self.B = batch_size or int(cfg.get("builder", {}).get("batch_size", 19))
-        self.grid, self.size = grid, tuple(size) if size else None
-        self.gen = torch.Generator().manual_seed(seed)
-        self.arrays: Optional[Dict[str, np.ndarray]] = None
-        if data is not None:
-            with np.load(str(data)) as z:
-                self.arrays = {k: z[k].astype(np.float32) for k in z.files}
-            need = {"rollout": ("data",), "pointcloud": ("xy", "rr", "sigma")}.get(self.kind, ("x", "y"))
-            if self.kind == "markov" and "data" in self.arrays:       # whole trajectories [n, M, N, T]: validation / test batches
-                if self.arrays["data"].ndim != 4:
-                    raise ValueError(f"{data}: a trajectory file holds data [n, M, N, T], got {self.arrays['data'].shape}")
-                if len(self.arrays["data"]) < self.B:
-                    raise ValueError(f"{data}: {len(self.arrays['data'])} trajectories do not fill one batch of {self.B}")
-                need = ("data",)
-            missing = [k for k in need if k not in self.arrays]
-            if missing:
-                raise ValueError(f"{data}: arrays {missing} missing (found {sorted(self.arrays)})")
-
-    def _rand(self, *shape):
-        return torch.randn(*shape, generator=self.gen).to(self.dev)
-
-    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
-        while True:
-            yield from self.epoch()
-
-    def epoch(self) -> Iterator[Dict[str, torch.Tensor]]:
-        if self.arrays is not None:
-            n = len(next(iter(self.arrays.values())))
-            nb = (n // self.B) // self.world * self.world        # the same number of batches on every rank
-            for i in range(self.rank * self.B, nb * self.B, self.world * self.B):
-                b = {k: torch.from_numpy(v[i:i + self.B]).to(self.dev) for k, v in self.arrays.items()}
-                yield self._finish(b)
-            return
-        yield self._finish(self._synthetic())
-
-    def _synthetic(self):
-        B, G, r = self.B, self.grid, self.routine
-        if self.kind == "rollout":
-            return dict(data=self._rand(B, G, G, 10 + r.n_steps))
-        if self.kind == "pointcloud":
-            n = self.size[0] if self.size else 972
-            return dict(xy=torch.rand(B, n, 2, generator=self.gen).to(self.dev), rr=self._rand(B, 42), sigma=self._rand(B, n, 1))
-        if self.kind == "mesh":
-            size = self.size or (G, G)
-            cin = r.model.input_dim - len(size)
-            return dict(x=self._rand(B, *size, cin), y=self._rand(B, *size, getattr(r.model, "output_dim", 1)))
-        b = dict(x=self._rand(B, G, G, 1), y=self._rand(B, G, G, 1))
-        if getattr(r, "append_force", False):
-            b["f"] = self._rand(B, G, G)
-        if getattr(r, "append_mu", False):
-            b["mu"] = torch.rand(B, generator=self.gen).to(self.dev)
-        return b
-
-    def _finish(self, b):
-        if self.kind == "rollout":      # the reference's forward() splits `data` and appends the positions (:38-50)
-            d = b["data"]
-            B, X, Y, _ = d.shape
-            xx = torch.cat([d[..., :10], self.routine._positions(B, X, Y, d.device)], dim=-1)
-            return dict(x=xx, y=d[..., 10:].contiguous())
-        return b
-
-    @property
-    def trajectories(self) -> bool:
-        return self.kind == "markov" and self.arrays is not None and "data" in self.arrays
+def _now(dev: torch.device) -> float:
+    """The wall clock once the work queued on the device is done: the two ends of every timed loop."""
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    return time.perf_counter()
 
 
-def _holds_trajectories(path: Path) -> bool:
-    with np.load(str(path)) as z:
-        return "data" in z.files
+def _open_run(run):
+    """The trial directory of a training run and where it starts: checkpoints and the log lines are rank 0's (every rank holds
+    the same weights and the same global normaliser statistics), so `run.out_dir` is None on the others and without logging;
+    --force deletes the old checkpoints (delete_old_results, commands/train.py:58); --resume continues from last.ckpt, which
+    every rank reads (`run.last`), and `run.start` is its epoch and global step."""
+    trial_dir = None if run.no_logging else _trial_dir(run.config_path.parent, run.trial, run.checkpoint_id, create=run.rank == 0)
+    run.out_dir = trial_dir if run.rank == 0 else None
+    if run.out_dir is not None and run.force and not run.resume:
+        for old in run.out_dir.glob("*.ckpt"):
+            old.unlink()
+    run.start, run.last = dict(epoch=0, global_step=0), None
+    if run.resume:
+        if trial_dir is None or not (trial_dir / "last.ckpt").exists():
+            raise FileNotFoundError("--resume needs checkpoints/trial-<trial>-*/last.ckpt (commands/train.py:74-80)")
+        run.last = trial_dir / "last.ckpt"
+        run.start = run.routine.resume_from_checkpoint(str(run.last))
+    return run.out_dir, run.start
 
 
-def _trajectory_batches(routine, cfg, dev, path: Path, batch_size: Optional[int], mode: str, k: int, **kw):
-    """The training set of a trajectory file on the device (builders/markov_data.py); `f` / `mu` go along when the routine
-    appends them."""
-    from .builders.markov_data import MarkovTrajectoryData
-    with np.load(str(path)) as z:
-        arrays = {name: z[name].astype(np.float32) for name in ("data", "f", "mu") if name in z.files}
-    missing = [name for name, on in (("f", routine.append_force), ("mu", routine.append_mu)) if on and name not in arrays]
-    if missing:
-        raise ValueError(f"{path}: arrays {missing} missing (found {sorted(arrays)})")
-    return MarkovTrajectoryData(arrays["data"], arrays.get("f") if routine.append_force else None,
-                                arrays.get("mu") if routine.append_mu else None, device=dev,
-                                batch_size=batch_size or int(cfg.get("builder", {}).get("batch_size", 19)), mode=mode, k=k, **kw)
+def _load_trained(config_path: Path, overrides, trial: int, map_location, device, accept=None):
+    """(cfg, routine, kind, ckpt): the routine of CONFIG with the weights of the trial's best checkpoint (or the
+    `checkpoint_path=...` override), on the device and under eval() -- trainer.test / predict run so: no statistics accumulation
+    (commands/test.py, normalizer.py:48).  `accept(routine, kind)`, where given, sees the routine before a checkpoint is looked
+    for: a command's own refusals come first."""
+    cfg = load_config(str(config_path), overrides or [])
+    dev = _device(device)
+    routine = build_routine(cfg).to(dev)
+    kind = routine_kind(routine)
+    if accept is not None:
+        accept(routine, kind)
+    ckpt = _best_checkpoint(config_path.parent, trial, cfg.get("checkpoint_path"))
+    routine.load_lightning_model_state(str(ckpt), map_location)
+    routine.to(dev)
+    routine.eval()
+    return cfg, routine, kind, ckpt
 
 
 # the classes `--builder` runs and the routine each one feeds
@@ -295,50 +243,33 @@ def _checkpoint_name(template: str, **values) -> str:
     return re.sub(r"\{([A-Za-z_]\w*)", r"\1={\1", template).format(**values) + ".ckpt"
 
 
-def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial, checkpoint_id, no_logging, force, resume, epochs,
-                        no_shuffle, drop_last, batch_size):
+def _train_from_builder(run, epochs, no_shuffle, drop_last, batch_size):
     """`train --builder`: whole epochs over the builder's training split, validation over its whole validation split after every
     epoch, the best checkpoint kept (CustomModelCheckpoint: monitor valid_loss, mode min, top 1), last.ckpt every epoch.  The
     Markov routine with `should_normalize` spends epoch 0 on the normaliser statistics alone (grid_2d_markov.py:374-390): no
     optimisation step is taken, `global_step` stands still, and the epoch is validated and checkpointed like any other."""
+    cfg, routine, kind, dev, rank, world = run.cfg, run.routine, run.kind, run.dev, run.rank, run.world
     bld = _instantiate_builder(cfg, kind, batch_size, routine)
     monitor, mode, template = _checkpoint_rule(cfg, bld)
     worst = math.inf if mode == "min" else -math.inf
     n_epochs = epochs or int((cfg.get("trainer") or {}).get("max_epochs", 0))
     if n_epochs < 1:
         raise ValueError("--builder runs whole epochs: pass --epochs E or set trainer.max_epochs in the config")
-    train_set = bld.train_data(dev, seed=7231 + trial, rank=rank, world=world, shuffle=not no_shuffle, drop_last=drop_last)
+    train_set = bld.train_data(dev, seed=7231 + run.trial, rank=rank, world=world, shuffle=not no_shuffle, drop_last=drop_last)
     valid_set = bld.valid_data(dev)      # every rank validates the whole split
-    trial_dir = None if no_logging else _trial_dir(config_path.parent, trial, checkpoint_id, create=rank == 0)
-    out_dir = trial_dir if rank == 0 else None
-    if out_dir is not None and force and not resume:
-        for old in out_dir.glob("*.ckpt"):
-            old.unlink()
-    start, best = dict(epoch=0, global_step=0), worst
-    if resume:
-        if trial_dir is None or not (trial_dir / "last.ckpt").exists():
-            raise FileNotFoundError("--resume needs checkpoints/trial-<trial>-*/last.ckpt (commands/train.py:74-80)")
-        start = routine.resume_from_checkpoint(str(trial_dir / "last.ckpt"))
+    (out_dir, start), best = _open_run(run), worst
+    if run.last is not None:
         # the best validation loss so far: last.ckpt carries it, as Lightning's carries its checkpoint callback's state
-        saved = torch.load(str(trial_dir / "last.ckpt"), map_location="cpu", weights_only=False).get("callbacks") or {}
+        saved = torch.load(str(run.last), map_location="cpu", weights_only=False).get("callbacks") or {}
         best = float((saved.get("ModelCheckpoint") or {}).get("best_model_score", worst))
-        for _ in range(start["epoch"] if train_set.shuffle else 0):      # the permutations of the epochs already run
-            train_set._epoch_ids()
-    if hasattr(routine, "current_epoch"):
-        routine.current_epoch = start["epoch"]
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
+        train_set.skip_epochs(start["epoch"])      # the permutations of the epochs already run
+    routine.current_epoch = start["epoch"]
+    t0 = _now(dev)
     gs = start["global_step"]
     for epoch in range(start["epoch"], n_epochs):
         loss = None
         for batch in train_set.epoch():
-            if kind == "markov":
-                loss = routine.training_step(batch, epoch=epoch)      # None in the statistics epoch
-            elif kind == "rollout":
-                loss = routine.training_step(batch, gs)[0]
-            else:
-                loss = routine.training_step(batch, gs)
+            loss = _train_step(routine, kind, batch, epoch, gs)      # None in the Markov routine's statistics epoch
             gs += loss is not None
         lv, lr = None if loss is None else float(loss.item()), routine.trainer().current_lr()
         if lv is not None and not math.isfinite(lv):
@@ -368,9 +299,7 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
             print(json.dumps(dict(epoch=epoch + 1, step=gs, train_loss=None if lv is None else round(lv, 6), lr=lr,
                                   valid_loss=round(vl, 6), best=improved, **{k: round(v, 6) for k, v in valid.items()})),
                   flush=True)
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    dt = _now(dev) - t0
     steps = gs - start["global_step"]
     if rank == 0:
         print(json.dumps(dict(steps=steps, batch=train_set.batch_size, world_size=world, epochs=n_epochs - start["epoch"],
@@ -381,11 +310,11 @@ def _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial
 
 
 def _train_step(routine, kind, batch, epoch, step):
-    if kind == "rollout":
-        return routine.training_step(batch, step)[0]
-    if kind in ("mesh", "pointcloud"):
-        return routine.training_step(batch, step)
-    return routine.training_step(batch, epoch=epoch)
+    """One training step of the routine -> its loss (the Markov routine's statistics epoch: None)."""
+    if kind == "markov":
+        return routine.training_step(batch, epoch=epoch)
+    out = routine.training_step(batch, step)
+    return out[0] if kind == "rollout" else out
 
 
 def _valid_loss(routine, kind, batch) -> float:
@@ -396,16 +325,11 @@ def _valid_loss(routine, kind, batch) -> float:
     routine.eval()
     try:
         with torch.no_grad():
-            if kind == "rollout":
-                return float(routine.validation_step(batch)["valid_loss"].item())
-            if kind in ("mesh", "pointcloud"):
-                return float(routine.validation_step(batch).item())
-            if "data" in batch:      # a trajectory batch: the reference's valid_loss, over the autoregressive rollout (:392-403)
-                return float(routine.validation_step(batch)["valid_loss"])
-            tr = routine.trainer()
-            pred = routine._unshuffle(tr.engine.forward(routine._shuffle(routine._build_features(batch, add_noise=False)), False))
-            target = (batch["dy"] if routine.learn_difference else batch["y"]).contiguous()
-            return float(tr.loss_and_grad(pred, target, routine._affine_tensor())[0].item())
+            if kind == "markov" and "data" not in batch:      # one-step pairs
+                return float(routine.pair_loss(batch).item())
+            # (Markov trajectory batch: the reference's valid_loss, over the autoregressive rollout, :392-403)
+            out = routine.validation_step(batch)
+            return float(out["valid_loss"] if isinstance(out, dict) else out)
     finally:
         routine.train(was_training)
 
@@ -466,32 +390,33 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     torch.manual_seed(int(cfg.get("seed", 7231 + trial)))      # commands/train.py:61-64 (the same initial weights on every rank)
     routine = build_routine(cfg).to(dev)
     _LAST["routine"] = routine
-    kind = _kind(routine)
+    kind = routine_kind(routine)
     if kind == "pointcloud" and world > 1:
         raise NotImplementedError("PointCloudExperiment: data parallel training is not built (one process, one GPU)")
+    run = SimpleNamespace(cfg=cfg, routine=routine, kind=kind, dev=dev, rank=rank, world=world, config_path=config_path, trial=trial,
+                          checkpoint_id=checkpoint_id, no_logging=no_logging, force=force, resume=resume)
     if builder:
         if data is not None or steps_per_epoch:
             raise ValueError("--builder takes its batches from the config's builder section and runs whole epochs: it goes with "
                              "neither --data nor --steps-per-epoch")
         if epochs < 0:
             raise ValueError("--epochs is a positive number of whole epochs")
-        return _train_from_builder(cfg, routine, kind, dev, rank, world, config_path, trial, checkpoint_id, no_logging, force, resume,
-                                   epochs, no_shuffle, drop_last, batch_size)
+        return _train_from_builder(run, epochs, no_shuffle, drop_last, batch_size)
     # a trajectory file is trained on when the command says how: any of the options below selects the pair rule and the epoch
     # order (each has a default); without one of them the file is refused as before
     as_trajectories = bool(epochs or no_shuffle or drop_last or pair_stride is not None or pair_mode is not None)
     if as_trajectories:
-        if kind != "markov" or data is None or not _holds_trajectories(data):
+        if kind != "markov" or data is None or not holds_trajectories(data):
             raise ValueError("--epochs, --no-shuffle, --drop-last, --pair-stride and --pair-mode need a trajectory training file: "
                              "the Markov routine with --data FILE holding data [n, M, N, T]")
         if epochs < 0 or (epochs and steps_per_epoch):
             raise ValueError("--epochs is a positive number of whole epochs and sets the epoch length itself (no --steps-per-epoch)")
-        batches = _trajectory_batches(routine, cfg, dev, data, batch_size, pair_mode or "ns_markov", 1 if pair_stride is None else pair_stride,
+        batches = trajectory_batches(routine, cfg, dev, data, batch_size, pair_mode or "ns_markov", 1 if pair_stride is None else pair_stride,
                                       seed=7231 + trial, shuffle=not no_shuffle, drop_last=drop_last, rank=rank, world=world)
         if epochs:
             steps, steps_per_epoch = epochs * len(batches), len(batches)
     else:
-        batches = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial, rank=rank, world=world)
+        batches = Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial, rank=rank, world=world)
         if batches.trajectories:
             raise ValueError(f"{data}: a trajectory file cannot be trained on as it is (training takes x / y pairs); pass it as "
                              f"--valid-data, or say how pairs are drawn from it: --pair-mode ns_markov|kolmogorov (or any of "
@@ -500,21 +425,11 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
     if valid_data is not None:
         if kind != "markov":
             raise ValueError("--valid-data takes the Markov routine's trajectory files; the other routines validate on --data")
-        valid = _Batches(routine, cfg, dev, valid_data, batch_size, grid, size, seed=7231 + trial)
+        valid = Batches(routine, cfg, dev, valid_data, batch_size, grid, size, seed=7231 + trial)
         if not valid.trajectories:
             raise ValueError(f"{valid_data}: no `data` [n, M, N, T] array (found {sorted(valid.arrays)})")
         valid_batch = next(iter(valid))
-    # checkpoints and the log lines are rank 0's (every rank holds the same weights and the same global normaliser statistics)
-    trial_dir = None if no_logging else _trial_dir(config_path.parent, trial, checkpoint_id, create=rank == 0)
-    out_dir = trial_dir if rank == 0 else None      # (only rank 0 writes; every rank reads the checkpoint it resumes from)
-    if out_dir is not None and force and not resume:
-        for old in out_dir.glob("*.ckpt"):       # delete_old_results (commands/train.py:58)
-            old.unlink()
-    start = dict(epoch=0, global_step=0)
-    if resume:
-        if trial_dir is None or not (trial_dir / "last.ckpt").exists():
-            raise FileNotFoundError("--resume needs checkpoints/trial-<trial>-*/last.ckpt (commands/train.py:74-80)")
-        start = routine.resume_from_checkpoint(str(trial_dir / "last.ckpt"))
+    out_dir, start = _open_run(run)
     it = iter(batches)
     epoch = start["epoch"]
     if kind == "markov" and not resume and routine.should_normalize:      # epoch 0: statistics only (:376-378)
@@ -523,11 +438,8 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
         epoch = max(epoch, 1)
     if epochs:      # whole epochs from here on: what the statistics pass left of its epoch is not trained on
         it = iter(batches)
-    if hasattr(routine, "current_epoch"):
-        routine.current_epoch = epoch
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
+    routine.current_epoch = epoch
+    t0 = _now(dev)
     loss = None
     for step in range(steps):
         loss = _train_step(routine, kind, next(it), epoch, step)
@@ -535,7 +447,7 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
             epoch += 1
             if hasattr(routine, "on_train_epoch_end"):
                 routine.on_train_epoch_end()
-            elif hasattr(routine, "current_epoch"):
+            else:      # the Markov routine: told the epoch by every training_step
                 routine.current_epoch = epoch
         if step % max(1, steps // 5) == 0 or step == steps - 1:
             lv = float(loss.item())
@@ -549,10 +461,8 @@ def train(config_path: Path, overrides: Optional[List[str]] = Argument(None), fo
             if rank == 0:
                 print(json.dumps(dict(step=start["global_step"] + step, epoch=epoch, train_loss=round(lv, 6),
                                       lr=routine.trainer().current_lr())), flush=True)
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    summary = dict(steps=steps, batch=batches.B if isinstance(batches, _Batches) else batches.batch_size, world_size=world,
+    dt = _now(dev) - t0
+    summary = dict(steps=steps, batch=batches.B if isinstance(batches, Batches) else batches.batch_size, world_size=world,
                    **(dict(epochs=epochs) if epochs else {}), steps_per_s=round(steps / max(dt, 1e-9), 2),
                    resumed_from_step=start["global_step"])
     if out_dir is not None:
@@ -588,14 +498,8 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
     for all test batches, and reports `pred_path` (the file written) and `pred_samples`."""
     if builder and data is not None:
         raise ValueError("--builder takes the test split from the config's builder section: it does not go with --data")
-    cfg = load_config(str(config_path), overrides or [])
+    cfg, routine, kind, ckpt = _load_trained(config_path, overrides, trial, map_location, device)
     dev = _device(device)
-    routine = build_routine(cfg).to(dev)
-    kind = _kind(routine)
-    ckpt = _best_checkpoint(config_path.parent, trial, cfg.get("checkpoint_path"))
-    routine.load_lightning_model_state(str(ckpt), map_location)
-    routine.to(dev)
-    routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
     if pred_path is not None:
         if kind != "markov":
             raise ValueError(f"--pred-path writes the test predictions of Grid2DMarkovExperiment; this config's routine is "
@@ -614,7 +518,7 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
         print(json.dumps(dict(checkpoint=str(ckpt), **{k: round(v, 6) for k, v in m.items()}, samples=test_set.n, **written)),
               flush=True)
         return
-    src = _Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial)
+    src = Batches(routine, cfg, dev, data, batch_size, grid, size, seed=7231 + trial)
     if parts is not None and not src.trajectories:      # one-step pairs or synthetic fields: test_step, which exports, does not run
         if pred_path is not None:
             raise ValueError("--pred-path: the predictions come from the trajectory rollout of test_step; give `--data TRAJ.npz` "
@@ -624,13 +528,11 @@ def test(config_path: Path, overrides: Optional[List[str]] = Argument(None), for
     acc: Dict[str, float] = {}
     for _ in range(batches):
         b = next(it)
-        if kind == "rollout":
-            m = {k: v for k, v in routine.test_step(b).items() if k in ("test_loss", "test_loss_avg", "test_time_until")}
-        elif src.trajectories:      # the reference's test metrics of the Markov routine (:408-416)
+        if kind == "rollout" or src.trajectories:      # (trajectories: the reference's test metrics of the Markov routine, :408-416)
             out = routine.test_step(b)
             if parts is not None:
                 parts(out)
-            m = {k: v for k, v in out.items() if k in ("test_loss", "test_loss_avg", "test_time_until", "test_corr")}
+            m = {k: v for k, v in out.items() if k in TEST_KEYS[kind]}
         else:
             m = {"test_loss": _valid_loss(routine, kind, b)}
         for k, v in m.items():
@@ -656,14 +558,8 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     predictions and report the time per model step (the reference's `inference_time`, commands/train.py:132-148)."""
     if builder and data is not None:
         raise ValueError("--builder takes the trajectories from the config's builder section: it does not go with --data")
-    cfg = load_config(str(config_path), overrides or [])
+    cfg, routine, kind, ckpt = _load_trained(config_path, overrides, trial, map_location, device)
     dev = _device(device)
-    routine = build_routine(cfg).to(dev)
-    kind = _kind(routine)
-    ckpt = _best_checkpoint(config_path.parent, trial, cfg.get("checkpoint_path"))
-    routine.load_lightning_model_state(str(ckpt), map_location)
-    routine.to(dev)
-    routine.eval()       # trainer.test / predict run under eval(): no statistics accumulation (commands/test.py, normalizer.py:48)
     traj = None
     if builder:
         if kind not in TEST_KEYS:
@@ -679,7 +575,7 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
         if chunk < 1:
             raise ValueError("--batch-size is at least 1")
     else:
-        b = next(iter(_Batches(routine, cfg, dev, data, batch_size or 1, grid, size, seed=7231 + trial)))
+        b = next(iter(Batches(routine, cfg, dev, data, batch_size or 1, grid, size, seed=7231 + trial)))
 
     def run():
         with torch.no_grad():
@@ -687,25 +583,22 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
                 parts = []
                 for lo in range(0, len(traj), chunk):
                     part = {"data": traj[lo:lo + chunk]}
+                    # (_valid_step here and _learning_step below: the routines' own names for the prediction pass; the one
+                    # place the commands reach for an underscore-prefixed member of a routine)
                     parts.append(routine._valid_step(part)[2] if kind == "markov" else routine.forward(part)[2])
                 return parts[0] if len(parts) == 1 else torch.cat(parts)
             if kind == "markov":
                 return routine.rollout(b["x"], n_steps, b.get("f"), b.get("mu"))
             if kind == "rollout":
-                routine.eval()
                 return routine._learning_step(b)[2]
             if kind == "pointcloud":
                 return routine(b)
             return routine.trainer().predict(b["x"])
 
     run()       # warm-up (routine.warmup() in the reference)
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
+    t0 = _now(dev)
     preds = run()
-    if dev.type == "cuda":
-        torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed = _now(dev) - t0
     steps = (n_steps or getattr(routine, "n_steps", None) or 1) if kind not in ("mesh", "pointcloud") else 1
     out = output or (ckpt.parent / "predictions.npz")
     np.savez(str(out), preds=preds.detach().cpu().numpy())
@@ -716,30 +609,6 @@ def predict(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
                      inference_time=elapsed / len(traj) / (routine.step_size * steps))
     print(json.dumps(dict(checkpoint=str(ckpt), predictions=str(out), shape=list(preds.shape),
                           inference_time_ms_per_step=round(1e3 * elapsed / steps, 4), **extra)), flush=True)
-
-
-def _initial_conditions(path: Path, routine) -> Dict[str, np.ndarray]:
-    """x0 [n, M, N] [, f, mu] of an initial-condition file: `x0`, `vorticity` or `data`, as [n, M, N] or -- a trajectory array
-    [n, M, N, T] -- its first time slice."""
-    with np.load(str(path)) as z:
-        name = next((k for k in ("x0", "vorticity", "data") if k in z.files), None)
-        if name is None:
-            raise ValueError(f"{path}: none of the arrays x0, vorticity, data (found {sorted(z.files)})")
-        x0 = z[name].astype(np.float32)
-        if x0.ndim == 4:
-            x0 = x0[..., 0]
-        if x0.ndim != 3:
-            raise ValueError(f"{path}: {name} must be [n, M, N] or [n, M, N, T], got {list(z[name].shape)}")
-        arrays = {"x0": np.ascontiguousarray(x0)}
-        missing = [k for k, on in (("f", routine.append_force), ("mu", routine.append_mu)) if on and k not in z.files]
-        if missing:
-            raise ValueError(f"{path}: arrays {missing} missing (found {sorted(z.files)}): the config appends them to the input")
-        for k, on in (("f", routine.append_force), ("mu", routine.append_mu)):
-            if on:
-                arrays[k] = z[k].astype(np.float32)
-                if len(arrays[k]) != len(x0):
-                    raise ValueError(f"{path}: {k} holds {len(arrays[k])} samples, {name} {len(x0)}")
-    return arrays
 
 
 @app.command()
@@ -756,20 +625,19 @@ def rollout(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
     `fourierflow infer`, commands/infer.py): `preds` [n, M, N, steps / every] and `times` = step_size * every * (1 .. L), one
     warm-up chunk, then the timed run; reports ms per model step and the reference's `inference_time` (seconds per sample and
     unit of simulated time)."""
-    cfg = load_config(str(config_path), overrides or [])
+    arrays = {}
+
+    def accept(routine, kind):
+        if kind != "markov":
+            raise ValueError(f"rollout runs the Markov routine (Grid2DMarkovExperiment); this config builds {type(routine).__name__}")
+        if batch_size is not None and batch_size < 1:
+            raise ValueError("--batch-size is at least 1")
+        if steps < 1 or every < 1 or steps % every:
+            raise ValueError(f"--steps is a positive multiple of --every, got --steps {steps} --every {every}")
+        arrays.update(initial_conditions(init, routine))
+
+    _, routine, _, ckpt = _load_trained(config_path, overrides, trial, map_location, device, accept)
     dev = _device(device)
-    routine = build_routine(cfg).to(dev)
-    if _kind(routine) != "markov":
-        raise ValueError(f"rollout runs the Markov routine (Grid2DMarkovExperiment); this config builds {type(routine).__name__}")
-    if batch_size is not None and batch_size < 1:
-        raise ValueError("--batch-size is at least 1")
-    if steps < 1 or every < 1 or steps % every:
-        raise ValueError(f"--steps is a positive multiple of --every, got --steps {steps} --every {every}")
-    arrays = _initial_conditions(init, routine)
-    ckpt = _best_checkpoint(config_path.parent, trial, cfg.get("checkpoint_path"))
-    routine.load_lightning_model_state(str(ckpt), map_location)
-    routine.to(dev)
-    routine.eval()
     n = len(arrays["x0"])
     chunk = min(batch_size or n, n)
     on_dev = {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
@@ -778,16 +646,10 @@ def rollout(config_path: Path, overrides: Optional[List[str]] = Argument(None), 
         part = {k: v[lo:lo + chunk] for k, v in on_dev.items()}
         return routine.simulate(part["x0"], steps, part.get("f"), part.get("mu"), every=every)
 
-    def sync():
-        if dev.type == "cuda":
-            torch.cuda.synchronize()
-
     run(0)      # warm-up: workspaces, weight packs
-    sync()
-    t0 = time.perf_counter()
+    t0 = _now(dev)
     parts = [run(lo) for lo in range(0, n, chunk)]
-    sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = _now(dev) - t0
     preds = parts[0] if len(parts) == 1 else torch.cat(parts)
     finite = bool(torch.isfinite(preds[..., -1]).all().item())      # the final field: one host read
     out = output or (ckpt.parent / "rollout.npz")
@@ -808,58 +670,6 @@ app.add_typer(generate_app, name="generate")
 @generate_app.callback()
 def _generate():
     """Generate datasets on the GPU (the reference's `fourierflow generate`, commands/generate.py)."""
-
-
-def _training_pairs(u: np.ndarray):
-    """u [n, M, N, T] -> x, y [(n (T - 1)), M, N, 1]: every snapshot with its successor, sample-major -- the (b t) order in which
-    the reference's NavierStokesTrainingDataset enumerates its pairs (builders/ns_contextual.py:57-72 with k = 1)."""
-    n, M, N, T = u.shape
-    x = np.ascontiguousarray(np.moveaxis(u[..., :-1], -1, 1)).reshape(n * (T - 1), M, N, 1)
-    y = np.ascontiguousarray(np.moveaxis(u[..., 1:], -1, 1)).reshape(n * (T - 1), M, N, 1)
-    return x, y
-
-
-class _NpzStream:
-    """An .npz file whose arrays are filled some rows at a time, so that host memory holds one batch and not the split: every
-    array is a memory-mapped .npy file in a scratch directory beside the output, and ``close()`` packs them, stored and not
-    compressed like ``np.savez``, into the .npz and returns their shapes."""
-
-    def __init__(self, out: str, rows: int):
-        import os
-        import tempfile
-        self.out, self.rows, self.arrays = out, rows, {}
-        self.scratch = tempfile.mkdtemp(prefix=os.path.basename(out) + ".", dir=os.path.dirname(out) or ".")
-
-    def array(self, name: str, tail) -> np.ndarray:
-        """The memory-mapped array ``name`` [rows, *tail], created on first use."""
-        import os
-        if name not in self.arrays:
-            self.arrays[name] = np.lib.format.open_memmap(os.path.join(self.scratch, name + ".npy"), mode="w+", dtype=np.float32,
-                                                          shape=(self.rows, *tail))
-        return self.arrays[name]
-
-    def put(self, name: str, row: int, block: np.ndarray):
-        self.array(name, block.shape[1:])[row:row + len(block)] = block
-
-    def abort(self):
-        """Drop what was written so far; no .npz is made."""
-        import shutil
-        self.arrays.clear()
-        shutil.rmtree(self.scratch, ignore_errors=True)
-
-    def close(self) -> Dict[str, List[int]]:
-        import os
-        import shutil
-        import zipfile
-        shapes = {name: list(a.shape) for name, a in self.arrays.items()}
-        for a in self.arrays.values():
-            a.flush()
-        self.arrays.clear()
-        with zipfile.ZipFile(self.out, "w", zipfile.ZIP_STORED, allowZip64=True) as z:
-            for name in shapes:
-                z.write(os.path.join(self.scratch, name + ".npy"), name + ".npy")
-        shutil.rmtree(self.scratch)
-        return shapes
 
 
 @generate_app.command("navier-stokes")
@@ -889,56 +699,15 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
     PATH.train.npz holds x / y pairs [, f, mu] (with --train-trajectories: whole trajectories like the other two), PATH.valid.npz
     and PATH.test.npz whole trajectories data [n, M, N, T], times [, f, mu].  `f` is written for --force random, `mu` when
     --mu-min and --mu-max differ.  Each split is solved --batch-size trajectories at a time, with a shorter last batch where that does not divide the split, and written batch by batch."""
-    import os
-
-    from typer import BadParameter
-
-    from .builders.synthetic import GaussianRF, solve_navier_stokes_2d
+    from .builders.synthetic import generate_navier_stokes
     if steps < 2:
         raise BadParameter("a training pair needs two snapshots", param_hint="--steps")
     if batch_size < 1 or ssr < 1:
         raise BadParameter("--batch-size and --ssr are at least 1")
-    dev = _device(device)
-    torch.manual_seed(seed)
-    np.random.seed(seed + 1234)
-    if os.path.dirname(path):
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-    field = GaussianRF(2, s, alpha=2.5, tau=7, device=dev)
-    n_solver = math.ceil(t / delta)
-    times = (np.arange(1, steps + 1) * (n_solver // steps) * delta).astype(np.float32)
-    vary_mu, pairs = mu_min != mu_max, steps - 1
-    written = {}
-    for split, n in (("train", n_train), ("valid", n_valid), ("test", n_test)):
-        if n <= 0:
-            continue
-        as_pairs = split == "train" and not train_trajectories
-        rows_per_sample = pairs if as_pairs else 1      # the per-sample f and mu are repeated for every pair
-        sink = _NpzStream(f"{path}.{split}.npz", n * rows_per_sample)
-        done = 0
-        while done < n:
-            b = min(batch_size, n - done)
-            # per batch, in this order: the initial vorticity from torch's generator; the viscosities, then (inside the solver)
-            # the seed of the random force from numpy's
-            with torch.no_grad():
-                w0 = field.sample(b)
-            nu = mu_min + (mu_max - mu_min) * np.random.rand(b) if vary_mu else mu
-            sol, f = solve_navier_stokes_2d(w0, nu, t, delta, steps, cycles, scaling, None, force, False)
-            sol = sol[:, ::ssr, ::ssr]
-            row = done * rows_per_sample
-            if as_pairs:
-                x, y = _training_pairs(sol)
-                sink.put("x", row, x)
-                sink.put("y", row, y)
-            else:
-                sink.put("data", row, sol)
-                sink.put("times", row, np.tile(times, (b, 1)))
-            if force == Force.random:
-                sink.put("f", row, np.repeat(f[:, ::ssr, ::ssr], rows_per_sample, axis=0))
-            if vary_mu:
-                sink.put("mu", row, np.repeat(nu, rows_per_sample))
-            done += b
-        written[split] = dict(file=sink.out, trajectories=n, **sink.close())
-    print(json.dumps(dict(solver_steps=n_solver, delta=delta, grid=s, ssr=ssr, **written)), flush=True)
+    summary = generate_navier_stokes(path, _device(device), n_train=n_train, n_valid=n_valid, n_test=n_test, s=s, t=t, steps=steps, mu=mu,
+                                     mu_min=mu_min, mu_max=mu_max, seed=seed, delta=delta, batch_size=batch_size, force=force,
+                                     cycles=cycles, scaling=scaling, ssr=ssr, train_trajectories=train_trajectories)
+    print(json.dumps(summary), flush=True)
 
 
 @generate_app.command("kolmogorov")
@@ -952,14 +721,12 @@ def kolmogorov(config_path: Path = Argument(..., help="a data-generation YAML of
     final fields, STEM_{size}.npz holding vorticity [n, size, size].  Otherwise (the trajectories files, started from
     `init_path`): STEM_{size}_{k}.npz holding vorticity [n, outer_steps // k, size, size], every k-th snapshot starting at the
     k-th, and time.  Sizes below the simulation grid are reduced through the staggered velocity, as the reference does."""
-    from typer import BadParameter
-
     from .builders.kolmogorov_flow import generate_kolmogorov, plan_kolmogorov
     if batch_size < 1:
         raise BadParameter("--batch-size is at least 1")
     plan = plan_kolmogorov(load_config(str(config_path), overrides or []), str(config_path))
     t0 = time.perf_counter()
-    written = generate_kolmogorov(plan, _device(device), batch_size, _NpzStream)
+    written = generate_kolmogorov(plan, _device(device), batch_size)
     print(json.dumps(dict(dt=plan.dt, steps=plan.solver_steps, grid=plan.N, trajectories=plan.n_trajectories,
                           elapsed=time.perf_counter() - t0, files=written)), flush=True)
 

@@ -24,11 +24,11 @@ import torch.nn as nn
 from .. import _capi, _lib, diagnostics
 from ..engine import _p
 from ..modules.normalizer import Normalizer
-from ..trainer import FFNOTrainer
 from .checkpoint import CheckpointMixin, reject_unsupported_routine_kwargs
+from .optimizer import OptimizerMixin
 
 
-class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
+class Grid2DMarkovExperiment(OptimizerMixin, CheckpointMixin, nn.Module):
     def __init__(self, conv: nn.Module, n_steps: Optional[int] = None, low: float = 0, high: float = 1,
                  use_position: bool = True, append_force: bool = False, append_mu: bool = False,
                  max_accumulations: float = 1e6, should_normalize: bool = True, use_fourier_position: bool = False,
@@ -75,32 +75,14 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         # reference's hard-coded 64: :433) with its energy spectrum; write_predictions writes them.  validation_step never does.
         self.pred_path = None if pred_path is None else str(pred_path)
         self.pred_size = diagnostics.check_size(pred_size, "pred_size")
-        self._opt_kw = dict(lr=2.5e-3, weight_decay=1e-4)
-        self._opt_kw.update(optimizer or {})
         # the F-FNO configs run cosine-with-warm-up per step; the FNOZongyi2DBlock ablations (torus_li/ablation/zongyi_markov*)
-        # run torch.optim.lr_scheduler.StepLR(step_size, gamma) per EPOCH -- recognised by its keyword arguments
-        self._step_lr = scheduler is not None and "step_size" in scheduler
-        self._sch_kw = dict(step_size=100, gamma=0.5) if self._step_lr else \
-            dict(num_warmup_steps=500, num_training_steps=100000, num_cycles=0.5)
-        self._sch_kw.update(scheduler or {})
-        self.current_epoch = 0
-        self._trainer: Optional[FFNOTrainer] = None
+        # run StepLR per EPOCH
+        self._init_optimizer(optimizer, scheduler, lr=2.5e-3, step_size=100, num_training_steps=100000)
         self._derived = None
         self._partial = None
         self._affine = None
 
     # ----------------------------------------------------------------------------------------------
-    def trainer(self) -> FFNOTrainer:
-        if self._trainer is None:
-            if self._step_lr:
-                tr = FFNOTrainer(self.conv, **self._opt_kw)
-                step, gamma = int(self._sch_kw["step_size"]), float(self._sch_kw["gamma"])
-                tr.lr_factor = lambda: gamma ** (self.current_epoch // step)
-                self._trainer = tr
-            else:
-                self._trainer = FFNOTrainer(self.conv, **self._opt_kw, **self._sch_kw)
-        return self._trainer
-
     def _build_features(self, batch: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None,
                         add_noise: bool = True) -> torch.Tensor:
         """x [B, M, N, Cx] -> normalised features [B, M, N, Cx + 2] (+ noise), accumulating the running
@@ -196,6 +178,15 @@ class Grid2DMarkovExperiment(CheckpointMixin, nn.Module):
         loss, gy = tr.loss_and_grad(pred, targets, self._affine_tensor())
         tr.apply_gradients(tr.engine.backward(self._shuffle(gy)))      # adjoint of the inverse gather = the forward gather
         return loss
+
+    @torch.no_grad()
+    def pair_loss(self, batch) -> torch.Tensor:
+        """The loss of one x / y pair batch without an optimisation step: features (no noise) -> conv on the inference engine ->
+        inverse-normalise -> LpLoss.rel.  Under eval() the normaliser statistics stand still."""
+        tr = self.trainer()
+        pred = self._unshuffle(tr.engine.forward(self._shuffle(self._build_features(batch, add_noise=False)), False))
+        target = (batch['dy'] if self.learn_difference else batch['y']).contiguous()
+        return tr.loss_and_grad(pred, target, self._affine_tensor())[0]
 
     def _shuffle(self, t: torch.Tensor) -> torch.Tensor:
         """x[:, x_idx][:, :, y_idx] (grid_2d_markov.py:177-178)."""

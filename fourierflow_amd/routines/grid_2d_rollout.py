@@ -16,11 +16,11 @@ import torch
 import torch.nn as nn
 
 from ..ops import lp_rel_loss
-from ..trainer import FFNOTrainer
 from .checkpoint import CheckpointMixin, reject_unsupported_routine_kwargs
+from .optimizer import EpochEndMixin
 
 
-class Grid2DRolloutExperiment(CheckpointMixin, nn.Module):
+class Grid2DRolloutExperiment(EpochEndMixin, CheckpointMixin, nn.Module):
     def __init__(self, conv: nn.Module, n_steps: int, k_max: int = 32, num_freq_bands: int = 8, freq_base: int = 2,
                  use_fourier_position: bool = False, append_pos: bool = True, teacher_forcing: bool = False,
                  step_size: float = 1.0, optimizer: Optional[dict] = None, scheduler: Optional[dict] = None, **unused):
@@ -31,24 +31,7 @@ class Grid2DRolloutExperiment(CheckpointMixin, nn.Module):
                                       "config of this routine and is not implemented")
         self.conv, self.n_steps = conv, n_steps
         self.append_pos, self.teacher_forcing, self.step_size = append_pos, teacher_forcing, step_size
-        self._opt_kw = dict(lr=2.5e-3, weight_decay=1e-4)
-        self._opt_kw.update(optimizer or {})
-        self._sch_kw = dict(step_size=100, gamma=0.5)            # StepLR of zongyi/4_layers/config.yaml:33-37
-        self._sch_kw.update(scheduler or {})
-        self.current_epoch = 0
-        self._trainer: Optional[FFNOTrainer] = None
-
-    # -- optimiser plumbing -------------------------------------------------------------------------
-    def trainer(self) -> FFNOTrainer:
-        if self._trainer is None:
-            tr = FFNOTrainer(self.conv, **self._opt_kw)
-            step, gamma = int(self._sch_kw["step_size"]), float(self._sch_kw["gamma"])
-            tr.lr_factor = lambda: gamma ** (self.current_epoch // step)      # torch.optim.lr_scheduler.StepLR, per epoch
-            self._trainer = tr
-        return self._trainer
-
-    def on_train_epoch_end(self):
-        self.current_epoch += 1
+        self._init_optimizer(optimizer, scheduler, lr=2.5e-3, step_size=100)      # StepLR of zongyi/4_layers/config.yaml:33-37
 
     # -- the rollout ----------------------------------------------------------------------------------
     @staticmethod

@@ -19,8 +19,8 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from ..trainer import FFNOTrainer
 from .checkpoint import CheckpointMixin, reject_unsupported_routine_kwargs
+from .optimizer import EpochEndMixin
 
 
 class _AutogradEngine:
@@ -84,7 +84,7 @@ class _TrainedParameters:
         return self._named
 
 
-class PointCloudExperiment(CheckpointMixin, nn.Module):
+class PointCloudExperiment(EpochEndMixin, CheckpointMixin, nn.Module):
     def __init__(self, model: nn.Module, iphi: nn.Module, N: int = 1000, optimizer: Optional[dict] = None,
                  scheduler: Optional[dict] = None, optimizer_type: str = "adamw", **unused):
         super().__init__()
@@ -92,31 +92,12 @@ class PointCloudExperiment(CheckpointMixin, nn.Module):
         if optimizer_type not in ("adamw", "adam"):
             raise NotImplementedError(f"optimizer_type={optimizer_type!r}: the fused step implements AdamW and Adam")
         self.model, self.iphi, self.N, self.optimizer_type = model, iphi, N, optimizer_type
-        self._opt_kw = dict(lr=1e-3, weight_decay=1e-4)
-        self._opt_kw.update(optimizer or {})
-        # the F-FNO configs run cosine-with-warm-up per step, the geo-FNO baseline (FNOPointCloud2D) torch.optim.Adam +
-        # StepLR(step_size, gamma) per EPOCH -- recognised by its keyword arguments
-        self._step_lr = scheduler is not None and "step_size" in scheduler
-        self._sch_kw = dict(step_size=50, gamma=0.5) if self._step_lr else \
-            dict(num_warmup_steps=500, num_training_steps=10000, num_cycles=0.5)
-        self._sch_kw.update(scheduler or {})
-        self.current_epoch = 0
-        self._trainer: Optional[FFNOTrainer] = None
+        # the F-FNO configs run cosine-with-warm-up per step, the geo-FNO baseline (FNOPointCloud2D) torch.optim.Adam + StepLR per
+        # EPOCH
+        self._init_optimizer(optimizer, scheduler, lr=1e-3, step_size=50, num_training_steps=10000)
 
-    def trainer(self) -> FFNOTrainer:
-        if self._trainer is None:
-            kw = dict(decoupled=self.optimizer_type == "adamw", **self._opt_kw)
-            if self._step_lr:
-                tr = FFNOTrainer(_TrainedParameters(self), **kw)
-                step, gamma = int(self._sch_kw["step_size"]), float(self._sch_kw["gamma"])
-                tr.lr_factor = lambda: gamma ** (self.current_epoch // step)
-                self._trainer = tr
-            else:
-                self._trainer = FFNOTrainer(_TrainedParameters(self), **kw, **self._sch_kw)
-        return self._trainer
-
-    def on_train_epoch_end(self):
-        self.current_epoch += 1
+    def _trainer_args(self):
+        return _TrainedParameters(self), dict(decoupled=self.optimizer_type == "adamw")
 
     def forward(self, batch):
         return self.model(batch['xy'], code=batch['rr'], iphi=self.iphi)

@@ -131,7 +131,7 @@ def test_one_upload_and_one_launch_per_batch(files, golden, host_device, monkeyp
     from fourierflow_amd import _capi
     from fourierflow_amd.builders import markov_data, sample_data
     uploads, launches = [], []
-    real_upload, real_check = markov_data._upload, _capi.check
+    real_upload, real_check = markov_data.upload, _capi.check
 
     def upload(t, device):
         uploads.append(t.numel())
@@ -142,7 +142,7 @@ def test_one_upload_and_one_launch_per_batch(files, golden, host_device, monkeyp
         return real_check(rc, what)
 
     for mod in (markov_data, sample_data):
-        monkeypatch.setattr(mod, "_upload", upload)
+        monkeypatch.setattr(mod, "upload", upload)
     monkeypatch.setattr(_capi, "check", check)
     bld = _builder(files["step"], golden)
     field = 3 * 4 * 4 * 7                                             # u after ssr = 2, and the per-step force

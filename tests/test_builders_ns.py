@@ -185,7 +185,7 @@ def test_one_upload_of_the_training_set_and_one_launch_per_batch(files, host_dev
     from fourierflow_amd.builders import NSMarkovBuilder, NSZongyiBuilder, markov_data, ns_data, sample_data
     path, u = files[16]
     uploads, launches = [], []
-    real_upload, real_check = markov_data._upload, _capi.check
+    real_upload, real_check = markov_data.upload, _capi.check
 
     def upload(t, device):
         uploads.append(t.numel())
@@ -196,7 +196,7 @@ def test_one_upload_of_the_training_set_and_one_launch_per_batch(files, host_dev
         return real_check(rc, what)
 
     for mod in (markov_data, sample_data, ns_data):
-        monkeypatch.setattr(mod, "_upload", upload)
+        monkeypatch.setattr(mod, "upload", upload)
     monkeypatch.setattr(_capi, "check", check)
     train_floats = u[:TRAIN].size
     for bld, what, n in ((NSMarkovBuilder(path, TRAIN, TEST, 1, batch_size=B), "markov_pairs", TRAIN * (T - 2)),

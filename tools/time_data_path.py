@@ -2,7 +2,7 @@
 """What the training data path costs per step of the Markov routine (markov/24: 24 layers, width 64, 16 modes; batch 32,
 64 x 64) on the GPU, with the batches coming from
 
-  (a) pairs:         an x / y / dx / dy pair file through the CLI's `_Batches` (a host slice and a synchronous copy per step),
+  (a) pairs:         an x / y / dx / dy pair file through `Batches` of builders/file_batches.py (a host slice and a synchronous copy per step),
   (b) trajectories:  the same set as whole trajectories through MarkovTrajectoryData (one ffno_markov_pairs launch per step,
                      a shuffled permutation per epoch),
   (c) fixed:         one batch that stays on the device (the floor `bench.py` measures),
@@ -24,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fourierflow_amd.builders.markov_data import MarkovTrajectoryData  # noqa: E402
-from fourierflow_amd.cli import _Batches  # noqa: E402
+from fourierflow_amd.builders.file_batches import Batches  # noqa: E402
 from fourierflow_amd.modules import FNOFactorized2DBlock  # noqa: E402
 from fourierflow_amd.routines import Grid2DMarkovExperiment  # noqa: E402
 
@@ -54,7 +54,7 @@ with tempfile.TemporaryDirectory() as tmp:
     path = os.path.join(tmp, "pairs.npz")
     np.savez(path, x=expand(data[..., 1:-1]), y=expand(data[..., 2:]), dx=expand(data[..., 1:-1] - data[..., :-2]),
              dy=expand(data[..., 2:] - data[..., 1:-1]))
-    pairs = _Batches(exp, {}, dev, path, B, G, None, seed=0)
+    pairs = Batches(exp, {}, dev, path, B, G, None, seed=0)
 trajectories = MarkovTrajectoryData(data, device=dev, batch_size=B, seed=0)
 fixed = next(iter(MarkovTrajectoryData(data, device=dev, batch_size=B, seed=0)))
 

@@ -4,7 +4,7 @@
 1. ms per training step on the airfoil geometry (221 x 51, batch 10, FNOFactorizedMesh2D of --layers layers, width 64), with the
    batches coming from
 
-  (a) npz:     an x / y file through the CLI's `_Batches` (a host slice and a synchronous copy per step, file order),
+  (a) npz:     an x / y file through `Batches` of builders/file_batches.py (a host slice and a synchronous copy per step, file order),
   (b) device:  the same samples through StructuredMesh2DBuilder -> DeviceSampleData (one ffno_sample_gather launch per step, a
                shuffled permutation per epoch),
   (c) fixed:   one batch that stays on the device,
@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fourierflow_amd.builders import ElasticityBuilder, PlasticityBuilder, StructuredMesh2DBuilder  # noqa: E402
 from fourierflow_amd.builders.sample_data import DeviceSampleData, Field  # noqa: E402
-from fourierflow_amd.cli import _Batches  # noqa: E402
+from fourierflow_amd.builders.file_batches import Batches  # noqa: E402
 from fourierflow_amd.modules import FNOFactorizedMesh2D  # noqa: E402
 from fourierflow_amd.routines import StructuredMeshExperiment  # noqa: E402
 
@@ -87,7 +87,7 @@ with tempfile.TemporaryDirectory() as tmp:
     exp = StructuredMeshExperiment(FNOFactorizedMesh2D(modes_x=32, modes_y=16, width=64, input_dim=4, n_layers=args.layers,
                                                        share_weight=False, factor=4, ff_weight_norm=True, n_ff_layers=2,
                                                        layer_norm=False)).to(dev)
-    npz = _Batches(exp, {}, dev, os.path.join(tmp, "train.npz"), B, 64, None, seed=0)
+    npz = Batches(exp, {}, dev, os.path.join(tmp, "train.npz"), B, 64, None, seed=0)
     device_set = airfoil.train_data(dev, seed=0)
     fixed = next(iter(airfoil.train_data(dev, seed=0)))
 
