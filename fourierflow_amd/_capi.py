@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 11
+ABI_VERSION = 12
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -310,6 +310,8 @@ SIGNATURES = {
     "ffno_ns2d_derivs": (I, [P, P, I, I, P]),
     "ffno_ns2d_advect": (I, [P, P, SZ, P]),
     "ffno_ns2d_cn_update": (I, [P, P, P, P, F, I, I, I, P]),
+    "ffno_ns2d_cn_update_harmonic": (I, [P, P, P, P, F, F, F, F, I, I, I, P]),
+    "ffno_ns2d_harmonic_force": (I, [P, P, F, F, F, I, I, I, P]),
     "ffno_kf2d_supported": (I, [I]),
     "ffno_kf2d_derivs": (I, [P, P, F, I, I, P]),
     "ffno_kf2d_stage": (I, [P, P, P, F, F, F, F, F, F, F, I, F, F, F, F, I, I, I, P]),

@@ -15,4 +15,4 @@ from .mesh_data import ElasticityBuilder, PlasticityBuilder, StructuredMesh2DBui
 from .ns_contextual import NSContextualBuilder  # noqa: F401
 from .ns_data import NSMarkovBuilder, NSZongyiBuilder  # noqa: F401
 from .sample_data import DeviceSampleData  # noqa: F401
-from .synthetic import Force, GaussianRF, random_force, solve_navier_stokes_2d  # noqa: F401
+from .synthetic import Force, GaussianRF, random_force, random_force_amplitudes, solve_navier_stokes_2d, solve_navier_stokes_2d_varying_force  # noqa: F401

@@ -689,6 +689,10 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
                   force: Force = Option(Force.li.value, help="forcing term of the vorticity equation"),
                   cycles: int = Option(2, help="--force random: harmonics per direction"),
                   scaling: float = Option(0.1, help="--force random: factor on the summed harmonics"),
+                  t_scaling: float = Option(0.2, help="--varying-force: the phase of the force is this times the time"),
+                  varying_force: bool = Option(False, "--varying-force",
+                                               help="--force random: advance the phase of the force with time, and write one "
+                                                    "force map per snapshot"),
                   ssr: int = Option(1, help="keep every ssr-th grid point of the solutions (the builders' stride subsampling)"),
                   train_trajectories: bool = Option(False, "--train-trajectories",
                                                     help="write PATH.train.npz as whole trajectories like the other two splits "
@@ -698,15 +702,22 @@ def navier_stokes(path: str = Argument(..., help="prefix of the files to write: 
     the Crank-Nicolson solver, the same options and seeding) and write them as the .npz files `train` / `test` / `predict` read:
     PATH.train.npz holds x / y pairs [, f, mu] (with --train-trajectories: whole trajectories like the other two), PATH.valid.npz
     and PATH.test.npz whole trajectories data [n, M, N, T], times [, f, mu].  `f` is written for --force random, `mu` when
-    --mu-min and --mu-max differ.  Each split is solved --batch-size trajectories at a time, with a shorter last batch where that does not divide the split, and written batch by batch."""
+    --mu-min and --mu-max differ.  With --varying-force (the `torus_vis_force` data) the random force gets the phase
+    --t-scaling times the time, a new field at every solver step, and `f` holds one map per snapshot: [n, M, N, steps] beside `data`
+    (column i is the force of the step that gave data[..., i]), and in the x / y form the map of each pair's y.  Each split is solved --batch-size trajectories at a time, with a shorter last batch where that does not divide the split, and written batch by batch."""
     from .builders.synthetic import generate_navier_stokes
     if steps < 2:
         raise BadParameter("a training pair needs two snapshots", param_hint="--steps")
     if batch_size < 1 or ssr < 1:
         raise BadParameter("--batch-size and --ssr are at least 1")
+    if varying_force and force != Force.random:
+        raise BadParameter("--varying-force goes with --force random (the only force with a phase to advance)", param_hint="--varying-force")
+    if varying_force and not 1 <= cycles < s // 2:
+        raise BadParameter(f"--varying-force: 1 <= cycles < s / 2 = {s // 2}", param_hint="--cycles")
     summary = generate_navier_stokes(path, _device(device), n_train=n_train, n_valid=n_valid, n_test=n_test, s=s, t=t, steps=steps, mu=mu,
                                      mu_min=mu_min, mu_max=mu_max, seed=seed, delta=delta, batch_size=batch_size, force=force,
-                                     cycles=cycles, scaling=scaling, ssr=ssr, train_trajectories=train_trajectories)
+                                     cycles=cycles, scaling=scaling, ssr=ssr, train_trajectories=train_trajectories, t_scaling=t_scaling,
+                                     varying_force=varying_force)
     print(json.dumps(summary), flush=True)
 
 

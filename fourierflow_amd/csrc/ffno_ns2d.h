@@ -5,6 +5,10 @@
 //     ffno_ns2d_advect     q w_x + v w_y on the four real fields                         (ns_2d.py:159, the product)
 //     (one rfft2)
 //     ffno_ns2d_cn_update  dealias, force, Crank-Nicolson update of w_h in place         (ns_2d.py:163, 173-175)
+// The time-varying random force (ns_2d.py:167-170, 203-237) is a sum of 3 cycles plane waves with fixed amplitudes and one common
+// phase phi = t_scaling t: in a half spectrum it has 4 cycles non-zero bins per sample, each a fixed amplitude rotated by
+// e^{+-i phi}.  ffno_ns2d_cn_update_harmonic is the update with those bins computed from amp[B][cycles][6] and (cos phi, sin phi)
+// -- no force field, no force transform, no f_h stream; ffno_ns2d_harmonic_force writes the field itself for the snapshots.
 // Wavenumbers come from the indices: row r is k_x = r (r < N/2) or r - N, column c is k_y = c; no tables.  The reference
 // transforms the FULL spectrum and keeps `.real`, which drops the derivative along an axis at that axis' Nyquist bin (the
 // products i k w there are anti-Hermitian); irfft2 would keep the row k_x = -N/2, so derivs writes zeros there.
@@ -108,6 +112,75 @@ __global__ __launch_bounds__(256) void ns2d_cn_kernel(float4* __restrict__ w, co
     }
 }
 
+// The harmonic force  scaling sum_p a1 sin(k x + phi) + a2 cos(k x + phi) + a3 sin(k y + phi) + a4 cos(k y + phi)
+// + a5 sin(k (x + y) + phi) + a6 cos(k (x + y) + phi),  k = 2 pi p, p = 1 .. cycles < N/2, in one bin of the unnormalised half
+// spectrum; a = amp of this sample [cycles][6], h = scaling N^2 / 2, e = cp + i sp.  Non-zero are (p, 0): h (a2 - i a1) e,
+// (N - p, 0): h (a2 + i a1) conj(e), (0, p): h (a4 - i a3) e and (p, p): h (a6 - i a5) e.
+__device__ __forceinline__ float2 harmonic_bin(const float* __restrict__ a, const Bin& b, int N, int cycles, float h, float cp,
+                                               float sp) {
+    float re, im, s = sp;
+    if (b.c == 0) {
+        if (b.r >= 1 && b.r <= cycles) a += 6 * (b.r - 1), re = a[1], im = -a[0];
+        else if (b.r >= N - cycles) a += 6 * (N - b.r - 1), re = a[1], im = a[0], s = -sp;
+        else return make_float2(0.f, 0.f);
+    } else if (b.c <= cycles) {
+        a += 6 * (b.c - 1);
+        if (b.r == 0) re = a[3], im = -a[2];
+        else if (b.r == b.c) re = a[5], im = -a[4];
+        else return make_float2(0.f, 0.f);
+    } else {
+        return make_float2(0.f, 0.f);
+    }
+    return make_float2(h * (re * cp - im * s), h * (re * s + im * cp));
+}
+
+// ns2d_cn_kernel with the force of a bin from harmonic_bin: a kernel of its own, so that the three modes above stay as they are
+__global__ __launch_bounds__(256) void ns2d_cn_harmonic_kernel(float4* __restrict__ w, const float4* __restrict__ F,
+                                                               const float* __restrict__ amp, const float* __restrict__ visc, float dt,
+                                                               float h, float cp, float sp, int cycles, unsigned pairs, int N, int lgN) {
+    const int Nh = N / 2 + 1;
+    for (unsigned p = blockIdx.x * 256u + threadIdx.x; p < pairs; p += gridDim.x * 256u) {
+        const float4 a = w[p], g = F[p];
+        Bin b(2u * p, N, Nh);
+        const unsigned s = b.row >> lgN;
+        const float* as = amp + (size_t)s * 6u * (unsigned)cycles;
+        const float hdn = 0.5f * dt * visc[s];
+        const float2 r0 = cn_bin(make_float2(a.x, a.y), make_float2(g.x, g.y), harmonic_bin(as, b, N, cycles, h, cp, sp), b, N, dt, hdn);
+        b.next(N, Nh);
+        const float2 r1 = cn_bin(make_float2(a.z, a.w), make_float2(g.z, g.w), harmonic_bin(as, b, N, cycles, h, cp, sp), b, N, dt, hdn);
+        w[p] = make_float4(r0.x, r0.y, r1.x, r1.y);
+    }
+}
+
+// one grid point of the harmonic force before the factor `scaling`: the grid angles 2 pi (p i mod N) / N are reduced exactly in
+// integers (N a power of two) and the phase comes in by the angle-sum formulas, so the error depends on neither p nor phi
+__device__ __forceinline__ float harmonic_point(const float* __restrict__ a, int i, int j, int N, int cycles, float cp, float sp) {
+    const float two_over_N = 2.f / (float)N;
+    float f = 0.f;
+    for (int p = 1; p <= cycles; ++p, a += 6) {
+        const int m[3] = {(p * i) & (N - 1), (p * j) & (N - 1), (p * (i + j)) & (N - 1)};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            float s, c;
+            plat::sincos_pi(two_over_N * (float)m[d], s, c);
+            f = fmaf(a[2 * d], fmaf(s, cp, c * sp), f);             // sin(theta + phi)
+            f = fmaf(a[2 * d + 1], fmaf(c, cp, -(s * sp)), f);      // cos(theta + phi)
+        }
+    }
+    return f;
+}
+
+__global__ __launch_bounds__(256) void ns2d_harmonic_force_kernel(const float* __restrict__ amp, float4* __restrict__ f, size_t n4,
+                                                                  float scaling, float cp, float sp, int cycles, int N, int lgN) {
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += (size_t)gridDim.x * 256) {
+        const size_t e = 4 * q;                                    // N is a multiple of 4: the four points share a row
+        const int j = (int)(e & (size_t)(N - 1)), i = (int)((e >> lgN) & (size_t)(N - 1));
+        const float* a = amp + (e >> (2 * lgN)) * 6u * (unsigned)cycles;
+        f[q] = make_float4(scaling * harmonic_point(a, i, j, N, cycles, cp, sp), scaling * harmonic_point(a, i, j + 1, N, cycles, cp, sp),
+                           scaling * harmonic_point(a, i, j + 2, N, cycles, cp, sp), scaling * harmonic_point(a, i, j + 3, N, cycles, cp, sp));
+    }
+}
+
 static inline int status() {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? FFNO_OK : (int)e;
@@ -118,6 +191,7 @@ static inline int log2_of(int N) {
     while ((1 << l) < N) ++l;
     return l;
 }
+static inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 static inline unsigned blocks_for(size_t items) {
     const size_t b = (items + 255) / 256;
     return (unsigned)(b < kMaxBlocks ? b : kMaxBlocks);
@@ -165,5 +239,30 @@ extern "C" int ffno_ns2d_cn_update(float* w_h, const float* F_h, const float* f_
     if (!f_h) FFNO_LAUNCH(ns2d_cn_kernel<0>, grid, dim3(256), 0, st, w, F, f, visc, delta_t, pairs, N, log2_of(N));
     else if (!f_batched) FFNO_LAUNCH(ns2d_cn_kernel<1>, grid, dim3(256), 0, st, w, F, f, visc, delta_t, pairs, N, log2_of(N));
     else FFNO_LAUNCH(ns2d_cn_kernel<2>, grid, dim3(256), 0, st, w, F, f, visc, delta_t, pairs, N, log2_of(N));
+    return status();
+}
+
+extern "C" int ffno_ns2d_cn_update_harmonic(float* w_h, const float* F_h, const float* amp, const float* visc, float delta_t,
+                                            float scaling, float cos_phi, float sin_phi, int cycles, int B, int N, void* stream) {
+    using namespace ffno::ns2d;
+    if (!w_h || !F_h || !amp || !visc || B <= 0 || N <= 0 || !aligned16(w_h) || !aligned16(F_h) || !aligned4(amp) || !aligned4(visc))
+        return FFNO_EINVAL;
+    const size_t bins = ffno_ns2d_supported(N) ? bins_of(B, N) : 0;
+    if (!bins || cycles < 1 || cycles >= N / 2) return FFNO_EUNSUPPORTED;
+    const unsigned pairs = (unsigned)(bins / 2);
+    FFNO_LAUNCH(ns2d_cn_harmonic_kernel, dim3(blocks_for(pairs)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(w_h),
+                reinterpret_cast<const float4*>(F_h), amp, visc, delta_t, scaling * (0.5f * (float)N * (float)N), cos_phi, sin_phi, cycles,
+                pairs, N, log2_of(N));
+    return status();
+}
+
+extern "C" int ffno_ns2d_harmonic_force(const float* amp, float* f, float scaling, float cos_phi, float sin_phi, int cycles, int B, int N,
+                                        void* stream) {
+    using namespace ffno::ns2d;
+    if (!amp || !f || B <= 0 || N <= 0 || !aligned4(amp) || !aligned16(f)) return FFNO_EINVAL;
+    if (!ffno_ns2d_supported(N) || !bins_of(B, N) || cycles < 1 || cycles >= N / 2) return FFNO_EUNSUPPORTED;
+    const size_t n4 = (size_t)B * N * N / 4;
+    FFNO_LAUNCH(ns2d_harmonic_force_kernel, dim3(blocks_for(n4)), dim3(256), 0, (hipStream_t)stream, amp, reinterpret_cast<float4*>(f),
+                n4, scaling, cos_phi, sin_phi, cycles, N, log2_of(N));
     return status();
 }

@@ -81,8 +81,8 @@ const char* ffno_build_target(void);
  * with; a caller compares it with the FFNO_ABI_VERSION it was compiled against before the first compute call (the Python host
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
  * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
- * in the same way. */
-#define FFNO_ABI_VERSION 11
+ * in the same way.  12: ffno_ns2d_cn_update_harmonic / ffno_ns2d_harmonic_force, likewise. */
+#define FFNO_ABI_VERSION 12
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -1234,6 +1234,21 @@ int ffno_pchead_bwd(const ffno_pchead_params* params, const ffno_pchead_params* 
  *       dealias = 1 where |k_x|, |k_y| <= (2/3)(N/2) (:109-113; 3 |k| <= N), else 0.  f_h: NULL (Force.none), one spectrum
  *       [N][N/2+1][2] for every sample (f_batched = 0) or [B][N][N/2+1][2] (f_batched = 1).  visc[B] on the device (a scalar
  *       viscosity is expanded by the host, :103-106).
+ * The time-varying random force (ns_2d.py:167-170, 203-237):
+ *         f = scaling sum_{p = 1 .. cycles} a1 sin(k x + phi) + a2 cos(k x + phi) + a3 sin(k y + phi) + a4 cos(k y + phi)
+ *                                         + a5 sin(k (x + y) + phi) + a6 cos(k (x + y) + phi),      k = 2 pi p,
+ *       on the grid x = i / N, y = j / N, with amp[B][cycles][6] = (a1 .. a6) per sample and cycle (the order of the reference's
+ *       draws) and the phase phi = t_scaling t given as cos_phi, sin_phi (computed by the host in double).  amp is a float
+ *       array (4-byte aligned).  cycles < 1 or cycles >= N / 2 (at p = N / 2 the rows p and N - p of the half spectrum coincide)
+ *       is FFNO_EUNSUPPORTED.
+ *   ffno_ns2d_cn_update_harmonic: ffno_ns2d_cn_update with f_h the unnormalised half spectrum of that force, computed in the
+ *       kernel and never stored: with h = scaling N^2 / 2 and e = cos_phi + i sin_phi its non-zero bins are, per sample and p,
+ *         (row p, column 0): h (a2 - i a1) e        (row N - p, column 0): h (a2 + i a1) conj(e)
+ *         (row 0, column p): h (a4 - i a3) e        (row p, column p):     h (a6 - i a5) e
+ *       and every other bin gets zero.  F_h, amp and visc are only read.
+ *   ffno_ns2d_harmonic_force: f[B][N][N] = that force on the grid (16-byte aligned).  The grid angles are reduced exactly,
+ *       2 pi ((p i) mod N) / N, and the phase is added by the angle-sum formulas, so the accuracy depends neither on p nor on
+ *       the size of phi.
  * Deterministic; no atomics, no workspace.
  * --------------------------------------------------------------------------------------------- */
 int ffno_ns2d_supported(int N);
@@ -1241,6 +1256,10 @@ int ffno_ns2d_derivs(const float* w_h, float* out4, int B, int N, void* stream);
 int ffno_ns2d_advect(const float* fields4, float* out, size_t n, void* stream);
 int ffno_ns2d_cn_update(float* w_h, const float* F_h, const float* f_h, const float* visc, float delta_t, int f_batched, int B,
                         int N, void* stream);
+int ffno_ns2d_cn_update_harmonic(float* w_h, const float* F_h, const float* amp, const float* visc, float delta_t, float scaling,
+                                 float cos_phi, float sin_phi, int cycles, int B, int N, void* stream);
+int ffno_ns2d_harmonic_force(const float* amp, float* f, float scaling, float cos_phi, float sin_phi, int cycles, int B, int N,
+                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The time step of the pseudo-spectral Kolmogorov-flow solver behind `generate kolmogorov` (reference builders/kolmogorov.py:328-428
