@@ -17,18 +17,12 @@ tests do to record launches) still sees the chain's launches.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 from typing import List, NamedTuple, Sequence
 
-import torch
-
 from . import _capi, _lib
 
-
-def _p(t):
-    """Pointer argument of a tensor; None and pointers that were made already pass through."""
-    return ctypes.c_void_p(t.data_ptr()) if isinstance(t, torch.Tensor) else t
+_p = _lib.ptr
 
 
 def checked(name, fn, *args):

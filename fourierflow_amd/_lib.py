@@ -94,6 +94,12 @@ def _install_test_backend(lib):
     _test_backend = lib
 
 
+def ptr(t):
+    """Pointer argument of a C-ABI call: a tensor's data pointer; None and pointers that were made already pass through."""
+    data_ptr = getattr(t, "data_ptr", None)      # (one attribute lookup, as t.data_ptr() would make: this is the launch path)
+    return t if data_ptr is None else ctypes.c_void_p(data_ptr())
+
+
 def current_stream(device) -> int:
     """hipStream_t of torch's current stream on ``device`` (0 for the emulator backend)."""
     if _test_backend is not None:

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from .. import _capi, _lib
-from ..engine import _p
+from .._lib import ptr as _p
 from .kolmogorov import load_initial, npz_path
 from .npz_stream import NpzStream
 

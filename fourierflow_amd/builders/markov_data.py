@@ -25,7 +25,7 @@ from typing import Dict
 import torch
 
 from .. import _capi, _lib
-from ..engine import _p as p
+from .._lib import ptr as p
 from .device_epochs import DeviceEpochs, tensor, upload
 
 MODES = ("ns_markov", "kolmogorov")

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from .. import _capi, _lib
-from ..engine import _p
+from .._lib import ptr as _p
 from .npz_stream import NpzStream
 
 

@@ -19,7 +19,7 @@ import torch
 
 from . import _capi, _lib
 from .builders.kolmogorov import npz_path
-from .engine import _p
+from ._lib import ptr as _p
 
 PRED_KEYS = ("pred_vorticity", "pred_vx", "pred_vy", "pred_energy_spectrum")
 MIN_SIZE, MAX_SIZE = 8, 256

@@ -29,6 +29,9 @@ import torch
 
 from . import _capi, _lib
 from ._corner_chain import CornerChain
+from ._engine_core import EngineCore
+
+_p = _lib.ptr
 
 MODES = {"full": 0, "low-pass": 1, "no-fourier": 2}
 HEAD_DIM = 128  # grid_2d.py:150-152 / mesh_3d.py:155-157: WNLinear(width, 128) -> WNLinear(128, out)
@@ -59,10 +62,6 @@ def _site_seed(*words: int) -> int:
     for w in words:
         h = _fmix32(h ^ _fmix32((int(w) + 0x7F4A7C15) & 0xFFFFFFFF))
     return h
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 class _StackRetry(Exception):
@@ -201,7 +200,7 @@ class _Workspace:
         self.stack_calls = 0             # ... launches so far
 
 
-class FFNOEngine:
+class FFNOEngine(EngineCore):
     """Kernel sequencer for one factorized-FNO configuration (fp32).
 
     spatial_dims = 2: FNOFactorized2DBlock -- fourier_weight[0] mixes the LAST axis, [1] the first
@@ -268,21 +267,21 @@ class FFNOEngine:
 
         # ---- parameter inventory, in the reference's named_parameters() naming --------------------
         self.linears: Dict[str, _Linear] = {}
-        self.param_shapes: Dict[str, Tuple[int, ...]] = {}
+        shapes: Dict[str, Tuple[int, ...]] = {}
 
         def add_linear(prefix, rows, cols):
             if prefix in self.linears:
                 return
             self.linears[prefix] = _Linear(prefix, rows, cols, ff_weight_norm)
             if ff_weight_norm:
-                self.param_shapes[prefix + "weight_g"] = (rows, 1)
-                self.param_shapes[prefix + "weight_v"] = (rows, cols)
+                shapes[prefix + "weight_g"] = (rows, 1)
+                shapes[prefix + "weight_v"] = (rows, cols)
             else:
-                self.param_shapes[prefix + "weight"] = (rows, cols)
-            self.param_shapes[prefix + "bias"] = (rows,)
+                shapes[prefix + "weight"] = (rows, cols)
+            shapes[prefix + "bias"] = (rows,)
             if layer_norm and prefix.endswith(f"_ff.layers.{self.n_ff - 1}.0."):   # the Sequential slot of the reference: layers.<last>.3
-                self.param_shapes[prefix[:-2] + "3.weight"] = (rows,)
-                self.param_shapes[prefix[:-2] + "3.bias"] = (rows,)
+                shapes[prefix[:-2] + "3.weight"] = (rows,)
+                shapes[prefix[:-2] + "3.bias"] = (rows,)
 
         add_linear("in_proj.", C, input_dim)
         self.ff_prefix: List[str] = []
@@ -309,17 +308,11 @@ class FFNOEngine:
                 names = tuple(base + str(w) for w in range(self.nd))
                 self.fw_names.append(names)
                 for w, n in enumerate(names):
-                    self.param_shapes.setdefault(n, (C, C, self.Ks[w], self.Ks[w], 2) if spectral == "plus"
-                                                 else (C, C, self.Ks[w]) if spectral == "dct" else (C, C, self.Ks[w], 2))
+                    shapes.setdefault(n, (C, C, self.Ks[w], self.Ks[w], 2) if spectral == "plus"
+                                      else (C, C, self.Ks[w]) if spectral == "dct" else (C, C, self.Ks[w], 2))
         add_linear("out.0.", HEAD_DIM, C)
         add_linear("out.1.", output_dim, HEAD_DIM)
-        self.param_names = list(self.param_shapes)
-        self.n_params = sum(int(np.prod(s)) for s in self.param_shapes.values())
-        self._offsets = {}
-        off = 0
-        for n in self.param_names:
-            self._offsets[n] = off
-            off += int(np.prod(self.param_shapes[n]))
+        self._lay_out(shapes)
         self._fw_sets: List[Tuple[str, ...]] = []   # unique weight tuples in first-use order
         for names in self.fw_names:
             if names not in self._fw_sets:
@@ -567,24 +560,6 @@ class FFNOEngine:
         else:
             self._k("ff_bwd_weights_partial", lib.ffno_ffx_bwd_weights_partial, *args, st)
 
-    def _k(self, name, fn, *args):
-        """Enqueue one C-ABI call; with a timer attached, bracket it with HIP events on the launch stream."""
-        t = self.timer
-        if t is not None and hasattr(t, "seen"):      # (an optional method of the timer protocol, which is not engine state)
-            t.seen(name, fn, args)          # bench.py: capture (entry point, arguments) for replay timing
-        rc = fn(*args) if t is None else self._timed(name, fn, *args)
-        if rc != 0:
-            _capi.check(rc, name)
-
-    def _timed(self, name, fn, *args) -> int:
-        t = self.timer
-        if t is None or not t.want(name):
-            return fn(*args)
-        t.start(name, self._issue_stream)
-        rc = fn(*args)
-        t.stop(name, self._issue_stream)
-        return rc
-
     # ------------------------------------------------------------------------------------------------
     def bind(self, params: Dict[str, torch.Tensor]):
         """Attach the parameter tensors (unique reference names -> fp32 contiguous device tensors)."""
@@ -593,20 +568,7 @@ class FFNOEngine:
         if sig is not None and self.params and sig == self._bind_sig:
             self.params = {n: params[n] for n in self.param_names}
             return
-        missing = [n for n in self.param_names if n not in params]
-        if missing:
-            raise KeyError(f"missing parameters: {missing[:4]}{'...' if len(missing) > 4 else ''}")
-        dev = None
-        for n in self.param_names:
-            t = params[n]
-            _lib.require_device_tensor(t, n)
-            if tuple(t.shape) != self.param_shapes[n]:
-                raise ValueError(f"{n}: expected shape {self.param_shapes[n]}, got {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"{n} must be contiguous")
-            dev = dev or t.device
-            if t.device != dev:
-                raise ValueError("all parameters must live on one device")
+        dev = self._validate(params)
         self.params = {n: params[n] for n in self.param_names}
         self._bind_sig = sig
         if dev != self.device:
@@ -636,10 +598,6 @@ class FFNOEngine:
                     if nb:
                         self.xplanes[si][w] = tuple(torch.empty(nb // 4, dtype=torch.int32, device=dev) for _ in range(2))
         self._reset_device_state()
-
-    def grad_view(self, name: str) -> torch.Tensor:
-        o = self._offsets[name]
-        return self.gflat[o:o + int(np.prod(self.param_shapes[name]))].view(self.param_shapes[name])
 
     def _refresh_pointers(self):
         sig = tuple(self.params[n].data_ptr() for n in self.param_names) + (self.ff_split,)

@@ -24,9 +24,9 @@ import torch
 
 from . import _capi, _lib
 from ._corner_chain import CornerChain
-from .engine import _p
 from .engine_zongyi import HEAD_DIM, ZongyiEngine
 
+_p = _lib.ptr
 ACT_NONE, ACT_GELU = 0, 2
 
 

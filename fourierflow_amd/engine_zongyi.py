@@ -16,17 +16,17 @@ from __future__ import annotations
 
 from typing import Dict
 
-import numpy as np
 import torch
 
 from . import _capi, _lib
 from ._corner_chain import CornerChain
-from .engine import _p
+from ._engine_core import EngineCore
 
+_p = _lib.ptr
 HEAD_DIM = 128
 
 
-class ZongyiEngine:
+class ZongyiEngine(EngineCore):
     def __init__(self, *, modes: int, width: int, input_dim: int, n_layers: int, residual: bool = False,
                  conv_residual: bool = True):
         if width > 32:
@@ -56,18 +56,14 @@ class ZongyiEngine:
     def _register(self, params):
         """``params``: (name, shape, pad geometry) in registration order; the pad geometry is (R, Cc, inner) of the plain tensor
         and (Rp, Cp) of its padded twin.  Lays out the flat gradient buffer and the padded twins."""
-        self.param_names = [n for n, _, _ in params]
-        self.param_shapes = {n: tuple(shape) for n, shape, _ in params}
+        self._lay_out({n: shape for n, shape, _ in params})
         self._pad_geom = {n: geom for n, _, geom in params}
-        self._offsets, off = {}, 0
         self._poffsets, poff = {}, 0
         for n in self.param_names:
-            self._offsets[n] = off
-            off += int(np.prod(self.param_shapes[n]))
             R, Cc, inner, Rp, Cp = self._pad_geom[n]
             self._poffsets[n] = poff
             poff += Rp * Cp * inner
-        self.n_params, self.n_padded = off, poff
+        self.n_padded = poff
 
     def _reset_state(self):
         """The state of an engine nothing is bound to yet."""
@@ -78,36 +74,14 @@ class ZongyiEngine:
         self.paired_last = False
         self._ws = {}
         self._ptr_sig = None
+        self._bound_sig = None      # data pointers of the tensors bound last
         self._packed = False
 
     # ------------------------------------------------------------------------------------------------
-    def _k(self, name, fn, *args):
-        t = self.timer
-        if t is not None and t.want(name):
-            t.start(name, self._issue_stream)
-            rc = fn(*args)
-            t.stop(name, self._issue_stream)
-        else:
-            rc = fn(*args)
-        if rc != 0:
-            _capi.check(rc, name)
-
     def bind(self, params: Dict[str, torch.Tensor]):
-        dev = None
-        for n in self.param_names:
-            if n not in params:
-                raise KeyError(f"missing parameter {n}")
-            t = params[n]
-            _lib.require_device_tensor(t, n)
-            if tuple(t.shape) != self.param_shapes[n]:
-                raise ValueError(f"{n}: expected shape {self.param_shapes[n]}, got {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"{n} must be contiguous")
-            dev = dev or t.device
-            if t.device != dev:
-                raise ValueError("all parameters must live on one device")
+        dev = self._validate(params)
         sig = tuple(params[n].data_ptr() for n in self.param_names)
-        if sig != getattr(self, "_bound_sig", None):
+        if sig != self._bound_sig:
             self._packed = False          # other tensors: the padded twins are stale whatever the caller says
         self._bound_sig = sig
         self.params = {n: params[n] for n in self.param_names}
@@ -126,10 +100,6 @@ class ZongyiEngine:
         """Start a fresh accumulation for backward(..., accumulate=True)."""
         self.gpad.zero_()
         self.gflat.zero_()
-
-    def grad_view(self, name: str) -> torch.Tensor:
-        o = self._offsets[name]
-        return self.gflat[o:o + int(np.prod(self.param_shapes[name]))].view(self.param_shapes[name])
 
     def _aliased(self, name) -> bool:
         """The padded twin has the parameter's own shape (width == channel tile): use the tensor itself, no copy."""

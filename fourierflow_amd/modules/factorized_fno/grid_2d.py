@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine import FFNO2DEngine
+from .._engine_module import EngineModule
 from ..feedforward import FeedForward
 from ..linear import WNLinear
 
@@ -55,37 +56,7 @@ class SpectralConv2d(nn.Module):
         return b, f
 
 
-class _BlockFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, module, *params):
-        eng = module._engine_for(params)
-        need_grad = ctx.needs_input_grad[0] or any(ctx.needs_input_grad[2:])
-        y = eng.forward(x, need_grad, training=module.training)      # (dropout follows nn.Module.training like the reference)
-        module._generation += 1
-        ctx.module, ctx.gen, ctx.n = module, module._generation, len(params)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        module = ctx.module
-        if module._generation != ctx.gen:
-            raise RuntimeError("FNOFactorized2DBlock: only the most recent forward pass can be back-propagated "
-                               "(activations live in one pre-allocated workspace)")
-        eng = module._engine
-        # the reference modules are ordinary autograd modules: dL/dx goes to whatever produced the input (grid_2d.py:154-177)
-        flat = eng.backward(gy.contiguous(), need_dx=ctx.needs_input_grad[0]).clone()
-        grads = []
-        off = 0
-        for n in eng.param_names:
-            cnt = 1
-            for s in eng.param_shapes[n]:
-                cnt *= s
-            grads.append(flat[off:off + cnt].view(eng.param_shapes[n]))
-            off += cnt
-        return (eng.dx if ctx.needs_input_grad[0] else None, None, *grads)
-
-
-class FNOFactorized2DBlock(nn.Module):
+class FNOFactorized2DBlock(EngineModule, nn.Module):
     def __init__(self, modes, width, input_dim=12, dropout=0.0, in_dropout=0.0, n_layers=4,
                  share_weight: bool = False, share_fork=False, factor=2, ff_weight_norm=False, n_ff_layers=2,
                  gain=1, layer_norm=False, use_fork=False, mode='full'):
@@ -117,10 +88,7 @@ class FNOFactorized2DBlock(nn.Module):
                 dropout=dropout, mode=mode))
 
         self.out = nn.Sequential(WNLinear(width, 128, wnorm=ff_weight_norm), WNLinear(128, 1, wnorm=ff_weight_norm))
-        self._engine = None
-        self._generation = 0
 
-    # -- engine plumbing ----------------------------------------------------------------------------
     def engine(self) -> FFNO2DEngine:
         if self._engine is None:
             self._engine = FFNO2DEngine(modes=self.modes, width=self.width, input_dim=self.input_dim,
@@ -130,39 +98,10 @@ class FNOFactorized2DBlock(nn.Module):
                                         dropout=self.dropout, in_dropout=self.in_dropout)
         return self._engine
 
-    def engine_parameters(self):
-        """Unique parameters in the engine's flat-buffer order (reference named_parameters() names)."""
-        eng = self.engine()
-        slots = self.__dict__.get("_param_slots")
-        if slots is None:
-            # where each engine parameter lives: (owning submodule, attribute).  The module tree is fixed after construction, so
-            # the walk over named_parameters() (0.3 ms of a 0.7 ms batch-1 forward) is done once; the Parameter objects are
-            # re-read from their owners on every call (a replaced or re-registered Parameter is seen).
-            owners = {}
-            for prefix, mod in self.named_modules():
-                for attr in mod._parameters:
-                    owners.setdefault(prefix + ("." if prefix else "") + attr, (mod, attr))
-            slots = [(n,) + owners[n] for n in eng.param_names]
-            self.__dict__["_param_slots"] = slots
-        return [(n, mod._parameters[attr]) for n, mod, attr in slots]
-
-    def prepare_input(self, x):
-        return x
-
-    def _engine_for(self, params):
-        eng = self.engine()
-        eng.bind({n: p.detach() for n, p in zip(eng.param_names, params)})
-        return eng
-
     def forward(self, x, **kwargs):
         # x.shape == [n_batches, *dim_sizes, input_size]; kwargs (global_step) are ignored like the reference
         _lib.require_device_tensor(x, "FNOFactorized2DBlock input")
-        params = [p for _, p in self.engine_parameters()]
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-            forecast = _BlockFn.apply(x, self, *params)
-        else:      # inference: no autograd node (a Function.apply over ~100 tensors costs as much as a third of the kernels)
-            forecast = self._engine_for(params).forward(x, False, training=self.training)
-            self._generation += 1
+        forecast = self._apply_engine(x)
         # forecast_list (per-layer head outputs, use_fork) is returned for logging like the reference does; gradients
         # flow through 'forecast' only
         flist = list(getattr(self._engine, "forecast_list", [])) if self.use_fork else []

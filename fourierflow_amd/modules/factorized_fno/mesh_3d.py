@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine import FFNOEngine
+from .._engine_module import EngineModule
 from ..feedforward import FeedForward
 from ..linear import WNLinear
 
@@ -38,32 +39,7 @@ class SpectralConv2d(nn.Module):
             self.backcast_ff = FeedForward(out_dim, factor, ff_weight_norm, n_ff_layers, layer_norm, dropout, general_ok=True)
 
 
-class _Mesh3DFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, module, *params):
-        eng = module._engine_for(params)
-        y = eng.forward(x, ctx.needs_input_grad[0] or any(ctx.needs_input_grad[2:]))
-        module._generation += 1
-        ctx.module, ctx.gen = module, module._generation
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        module = ctx.module
-        if module._generation != ctx.gen:
-            raise RuntimeError("FNOFactorizedMesh3D: only the most recent forward pass can be back-propagated")
-        eng = module._engine
-        # the reference modules are ordinary autograd modules: dL/dx goes to whatever produced the input (grid_2d.py:154-177)
-        flat = eng.backward(gy.contiguous(), need_dx=ctx.needs_input_grad[0]).clone()
-        grads, off = [], 0
-        for n in eng.param_names:
-            cnt = int(np.prod(eng.param_shapes[n]))
-            grads.append(flat[off:off + cnt].view(eng.param_shapes[n]))
-            off += cnt
-        return (eng.dx if ctx.needs_input_grad[0] else None, None, *grads)
-
-
-class FNOFactorizedMesh3D(nn.Module):
+class FNOFactorizedMesh3D(EngineModule, nn.Module):
     def __init__(self, modes_x, modes_y, modes_z, width, input_dim, output_dim, n_layers, share_weight, factor,
                  ff_weight_norm, n_ff_layers, layer_norm):
         super().__init__()
@@ -89,8 +65,6 @@ class FNOFactorizedMesh3D(nn.Module):
                                  WNLinear(128, output_dim, wnorm=ff_weight_norm))
         self.layer_norm = bool(layer_norm)
         self.n_ff_layers = n_ff_layers
-        self._engine = None
-        self._generation = 0
 
     def engine(self) -> FFNOEngine:
         if self._engine is None:
@@ -100,15 +74,6 @@ class FNOFactorizedMesh3D(nn.Module):
                                       ff_weight_norm=self.ff_weight_norm, mode="full", spatial_dims=3,
                                       padding=self.padding, output_dim=self.output_dim, layer_norm=self.layer_norm, n_ff_layers=self.n_ff_layers)
         return self._engine
-
-    def engine_parameters(self):
-        named = dict(self.named_parameters())
-        return [(n, named[n]) for n in self.engine().param_names]
-
-    def _engine_for(self, params):
-        eng = self.engine()
-        eng.bind({n: p.detach() for n, p in zip(eng.param_names, params)})
-        return eng
 
     def get_grid(self, shape, device):
         B, X, Y, Z = shape[0], shape[1], shape[2], shape[3]
@@ -126,6 +91,4 @@ class FNOFactorizedMesh3D(nn.Module):
 
     def forward(self, x):
         _lib.require_device_tensor(x, "FNOFactorizedMesh3D input")
-        x = self.prepare_input(x)   # [B, X, Y, Z, input_dim]
-        params = [p for _, p in self.engine_parameters()]
-        return _Mesh3DFn.apply(x, self, *params)
+        return self._apply_engine(self.prepare_input(x))   # [B, X, Y, Z, input_dim]

@@ -98,7 +98,7 @@ class Normalizer(nn.Module):
         axis.  Runs the fused HIP statistics / normalise kernel of the Markov routine on the flattened [pixels, D] view."""
         import ctypes
         from .. import _capi, _lib
-        from ..engine import _p
+        from .._lib import ptr as _p
         _lib.require_device_tensor(x, "Normalizer input")
         D = self.sum.numel()
         if x.shape[-1] != D:

@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine_zongyi import ZongyiEngine
+from .._engine_module import EngineModule
 
 
 class SpectralConv2d(nn.Module):
@@ -30,42 +31,7 @@ class SpectralConv2d(nn.Module):
         raise RuntimeError("layers of FNOZongyi2DBlock run inside the block's fused HIP pass; call the block")
 
 
-class _ZongyiFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, module, *params):
-        eng = module._engine_for(params)
-        need_grad = any(ctx.needs_input_grad)
-        slot = 0
-        if need_grad:
-            slot = module._next_slot()
-        y = eng.forward(x, need_grad, slot=slot, n_slots=module.max_live_passes, weights_ready=module.weights_frozen)
-        ctx.module, ctx.slot, ctx.ticket = module, slot, module._tickets[slot] if need_grad else None
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        module = ctx.module
-        if module._tickets[ctx.slot] != ctx.ticket:
-            raise RuntimeError(f"FNOZongyi2DBlock: more than max_live_passes={module.max_live_passes} forward passes were "
-                               "alive at once; raise module.max_live_passes")
-        eng = module._engine
-        need_dx = ctx.needs_input_grad[0]
-        if module.fused_grad_accumulation:      # the routine reads eng.gflat after the whole graph ran (eng.zero_grad() first)
-            res = eng.backward(gy.contiguous(), slot=ctx.slot, need_dx=need_dx, accumulate=True)
-            return (res[1] if need_dx else None, None, *([None] * len(eng.param_names)))
-        flat, dx = eng.backward(gy.contiguous(), slot=ctx.slot, need_dx=True)
-        flat = flat.clone()
-        grads, off = [], 0
-        for n in eng.param_names:
-            cnt = 1
-            for s in eng.param_shapes[n]:
-                cnt *= s
-            grads.append(flat[off:off + cnt].view(eng.param_shapes[n]))
-            off += cnt
-        return (dx if ctx.needs_input_grad[0] else None, None, *grads)
-
-
-class FNOZongyi2DBlock(nn.Module):
+class FNOZongyi2DBlock(EngineModule, nn.Module):
     def __init__(self, modes1, modes2, width, input_dim=12, dropout=0.1, n_layers=4, residual=False, conv_residual=True):
         super().__init__()
         if modes1 != modes2:
@@ -77,30 +43,16 @@ class FNOZongyi2DBlock(nn.Module):
             SpectralConv2d(in_dim=width, out_dim=width, n_modes=modes1, resdiual=conv_residual, dropout=dropout)
             for _ in range(n_layers)])
         self.feedforward = nn.Sequential(nn.Linear(width, 128), nn.ReLU(inplace=True), nn.Linear(128, 1))
-        self._engine = None
         self.weights_frozen = False              # True: the padded / packed weights of the last pass are still valid
         self.fused_grad_accumulation = False     # True: parameter gradients accumulate in engine().gflat, .grad stays None
         self.max_live_passes = 16       # forward passes that may await their backward at once (rollout: n_steps)
         self._tickets, self._cursor, self._ticket = {}, 0, 0
 
-    # -- engine plumbing ----------------------------------------------------------------------------
     def engine(self) -> ZongyiEngine:
         if self._engine is None:
             self._engine = ZongyiEngine(modes=self.modes1, width=self.width, input_dim=self.input_dim, n_layers=self.n_layers,
                                         residual=self.residual, conv_residual=self.conv_residual)
         return self._engine
-
-    def engine_parameters(self):
-        named = dict(self.named_parameters())
-        return [(n, named[n]) for n in self.engine().param_names]
-
-    def prepare_input(self, x):
-        return x
-
-    def _engine_for(self, params):
-        eng = self.engine()
-        eng.bind({n: p.detach() for n, p in zip(eng.param_names, params)})
-        return eng
 
     def _next_slot(self):
         slot = self._cursor % self.max_live_passes
@@ -109,8 +61,23 @@ class FNOZongyi2DBlock(nn.Module):
         self._tickets[slot] = self._ticket
         return slot
 
+    # -- several passes alive at once: a slot and a ticket per saved pass instead of the generation count -----------------
+    def _run_forward(self, eng, x, save):
+        slot = self._next_slot() if save else 0
+        y = eng.forward(x, save, slot=slot, n_slots=self.max_live_passes, weights_ready=self.weights_frozen)
+        return y, (slot, self._tickets[slot] if save else None)
+
+    def _run_backward(self, eng, token, gy, need_dx):
+        slot, ticket = token
+        if self._tickets[slot] != ticket:
+            raise RuntimeError(f"FNOZongyi2DBlock: more than max_live_passes={self.max_live_passes} forward passes were "
+                               "alive at once; raise module.max_live_passes")
+        if self.fused_grad_accumulation:      # the routine reads eng.gflat after the whole graph ran (eng.zero_grad() first)
+            res = eng.backward(gy, slot=slot, need_dx=need_dx, accumulate=True)
+            return None, res[1] if need_dx else None
+        return eng.backward(gy, slot=slot, need_dx=True)
+
     def forward(self, x, **kwargs):
         # x.shape == [n_batches, *dim_sizes, input_size]
         _lib.require_device_tensor(x, "FNOZongyi2DBlock input")
-        params = [p for _, p in self.engine_parameters()]
-        return {'forecast': _ZongyiFn.apply(x, self, *params)}
+        return {'forecast': self._apply_engine(x)}

@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine_geofno import GeoFNO2DEngine
+from .._engine_module import EngineModule
 
 
 class _ComplexCornerWeights(nn.Module):
@@ -50,39 +51,23 @@ class SpectralConv2d(_ComplexCornerWeights):
         self.modes1, self.modes2 = modes1, modes2
 
 
-class _MeshFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, module, *params):
-        eng = module._engine_for(params)
-        need_grad = any(ctx.needs_input_grad[2:])
-        y = eng.forward(x, need_grad)
-        module._generation += 1
-        ctx.module, ctx.gen = module, module._generation
-        return y
+class _GeoMeshModule(EngineModule):
+    """The GeoFNO engines take no dropout switch and compute no input gradient."""
 
-    @staticmethod
-    def backward(ctx, gy):
-        module = ctx.module
-        if ctx.needs_input_grad[0]:
+    def _run_forward(self, eng, x, save):
+        return eng.forward(x, save), self._new_pass()
+
+    def _run_backward(self, eng, token, gy, need_dx):
+        if need_dx:
             # the reference modules are ordinary autograd modules and would propagate dL/dx; this operator's kernels stop at
             # the lift's parameter gradients -- fail loudly instead of silently training upstream parameters without that term
-            raise RuntimeError(f"{type(module).__name__}: the gradient with respect to the INPUT tensor is not computed by the "
+            raise RuntimeError(f"{type(self).__name__}: the gradient with respect to the INPUT tensor is not computed by the "
                                "gfx950 kernel set (feed it a tensor that does not require grad)")
-        if module._generation != ctx.gen:
-            raise RuntimeError("FNOMesh2D / FNOMesh3D: only the most recent forward pass can be back-propagated")
-        eng = module._engine
-        flat = eng.backward(gy.contiguous()).clone()
-        grads, off = [], 0
-        for n in eng.param_names:
-            cnt = 1
-            for s in eng.param_shapes[n]:
-                cnt *= s
-            grads.append(flat[off:off + cnt].view(eng.param_shapes[n]))
-            off += cnt
-        return (None, None, *grads)
+        self._check_latest(token)
+        return eng.backward(gy), None
 
 
-class FNOMesh2D(nn.Module):
+class FNOMesh2D(_GeoMeshModule, nn.Module):
     def __init__(self, modes1, modes2, width, n_layers):
         super().__init__()
         self.modes1, self.modes2, self.width, self.n_layers = modes1, modes2, width, n_layers
@@ -93,18 +78,11 @@ class FNOMesh2D(nn.Module):
         self.ws = nn.ModuleList([nn.Conv2d(width, width, 1) for _ in range(n_layers)])
         self.fc1 = nn.Linear(width, 128)
         self.fc2 = nn.Linear(128, 1)
-        self._engine = None
-        self._generation = 0
 
-    # -- engine plumbing ----------------------------------------------------------------------------
     def engine(self) -> GeoFNO2DEngine:
         if self._engine is None:
             self._engine = GeoFNO2DEngine(modes1=self.modes1, modes2=self.modes2, width=self.width, n_layers=self.n_layers)
         return self._engine
-
-    def engine_parameters(self):
-        named = dict(self.named_parameters())
-        return [(n, named[n]) for n in self.engine().param_names]
 
     def get_grid(self, shape, device):
         B, X, Y = shape[0], shape[1], shape[2]
@@ -115,12 +93,6 @@ class FNOMesh2D(nn.Module):
     def prepare_input(self, x):
         return torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).contiguous()
 
-    def _engine_for(self, params):
-        eng = self.engine()
-        eng.bind({n: p.detach() for n, p in zip(eng.param_names, params)})
-        return eng
-
     def forward(self, x):
         _lib.require_device_tensor(x, "FNOMesh2D input")
-        params = [p for _, p in self.engine_parameters()]
-        return _MeshFn.apply(self.prepare_input(x), self, *params)
+        return self._apply_engine(self.prepare_input(x))

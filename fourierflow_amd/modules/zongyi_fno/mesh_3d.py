@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine_geofno import GeoFNO3DEngine
-from .mesh_2d import _ComplexCornerWeights, _MeshFn
+from .mesh_2d import _ComplexCornerWeights, _GeoMeshModule
 
 
 class SpectralConv3d(_ComplexCornerWeights):
@@ -21,7 +21,7 @@ class SpectralConv3d(_ComplexCornerWeights):
         self.modes1, self.modes2, self.modes3 = modes1, modes2, modes3
 
 
-class FNOMesh3D(nn.Module):
+class FNOMesh3D(_GeoMeshModule, nn.Module):
     def __init__(self, modes1, modes2, modes3, width, n_layers=4):
         super().__init__()
         self.modes1, self.modes2, self.modes3, self.width, self.n_layers = modes1, modes2, modes3, width, n_layers
@@ -32,19 +32,12 @@ class FNOMesh3D(nn.Module):
         self.ws = nn.ModuleList([nn.Conv3d(width, width, 1) for _ in range(n_layers)])
         self.fc1 = nn.Linear(width, 128)
         self.fc2 = nn.Linear(128, 4)
-        self._engine = None
-        self._generation = 0
 
-    # -- engine plumbing ----------------------------------------------------------------------------
     def engine(self) -> GeoFNO3DEngine:
         if self._engine is None:
             self._engine = GeoFNO3DEngine(modes1=self.modes1, modes2=self.modes2, modes3=self.modes3, width=self.width,
                                           n_layers=self.n_layers)
         return self._engine
-
-    def engine_parameters(self):
-        named = dict(self.named_parameters())
-        return [(n, named[n]) for n in self.engine().param_names]
 
     def get_grid(self, shape, device):
         B, X, Y, Z = shape[0], shape[1], shape[2], shape[3]
@@ -56,12 +49,6 @@ class FNOMesh3D(nn.Module):
     def prepare_input(self, x):
         return torch.cat((x, self.get_grid(x.shape, x.device)), dim=-1).contiguous()
 
-    def _engine_for(self, params):
-        eng = self.engine()
-        eng.bind({n: p.detach() for n, p in zip(eng.param_names, params)})
-        return eng
-
     def forward(self, x):
         _lib.require_device_tensor(x, "FNOMesh3D input")
-        params = [p for _, p in self.engine_parameters()]
-        return _MeshFn.apply(self.prepare_input(x), self, *params)
+        return self._apply_engine(self.prepare_input(x))

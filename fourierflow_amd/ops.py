@@ -14,7 +14,8 @@ import torch
 
 from . import _capi, _lib
 from ._corner_chain import CornerChain, checked
-from .engine import MODES, _p
+from ._lib import ptr as _p
+from .engine import MODES
 
 
 _SP2D_WS = {}

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import _capi, _lib, diagnostics
-from ..engine import _p
+from .._lib import ptr as _p
 from ..modules.normalizer import Normalizer
 from .checkpoint import CheckpointMixin, reject_unsupported_routine_kwargs
 from .optimizer import OptimizerMixin
@@ -288,7 +288,7 @@ class Grid2DMarkovExperiment(OptimizerMixin, CheckpointMixin, nn.Module):
         traj = torch.empty(B, M, N, n_steps // every, dtype=torch.float32, device=dev)
         fused = not (self.use_velocity or self.shuffle_grid)
         tr = self.trainer()
-        view = {"own_output": False} if getattr(tr.engine, "can_return_view", False) else {}
+        view = {"own_output": False} if tr.engine.can_return_view else {}
         D = self.conv.input_dim
         was_training = self.normalizer.training
         self.normalizer.eval()

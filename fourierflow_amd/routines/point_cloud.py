@@ -28,6 +28,8 @@ class _AutogradEngine:
     gradient, weights_changed) over a model whose forward pass is a composition of autograd ops: backward is
     ``torch.autograd.backward`` into views of the flat gradient buffer."""
 
+    can_return_view = False
+
     def __init__(self, named):
         self.param_names = [n for n, _ in named]
         self.param_shapes = {n: tuple(p.shape) for n, p in named}

@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import _capi, _lib
-from .engine import _p
+from ._lib import ptr as _p
 
 
 def cosine_warmup_factor(step: int, num_warmup_steps: int, num_training_steps: int, num_cycles: float = 0.5) -> float:
@@ -107,7 +107,7 @@ class FFNOTrainer:
         target = target.contiguous()
         # (the prediction is consumed by the loss kernel at once: a view of the engine's output buffer, not a copy; the loss lands in
         #  a tensor of its own: two copy launches less per step than forward() + loss.clone())
-        if getattr(self.engine, "can_return_view", False):
+        if self.engine.can_return_view:
             pred = self.engine.forward(self.block.prepare_input(x), True, own_output=False)
         else:
             pred = self.engine.forward(self.block.prepare_input(x), True)
@@ -139,8 +139,7 @@ class FFNOTrainer:
         _capi.check(fn(_p(self.pflat), _p(gflat), _p(self.m), _p(self.v), self.pflat.numel(), lr_t, self.betas[0],
                        self.betas[1], self.eps, self.wd, self.opt_step, 1.0 / self.world,
                        _lib.current_stream(self.device)), "adamw" if self.decoupled else "adam")
-        if hasattr(self.engine, "weights_changed"):
-            self.engine.weights_changed()      # (the kernel wrote the parameters through a raw pointer)
+        self.engine.weights_changed()      # (the kernel wrote the parameters through a raw pointer)
         return loss_out
 
     @torch.no_grad()

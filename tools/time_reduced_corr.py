@@ -29,7 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from fourierflow_amd import _capi, _lib  # noqa: E402
-from fourierflow_amd.engine import _p  # noqa: E402
+from fourierflow_amd._lib import ptr as _p  # noqa: E402
 from fourierflow_amd.modules import FNOFactorized2DBlock  # noqa: E402
 from fourierflow_amd.routines import Grid2DMarkovExperiment  # noqa: E402
 

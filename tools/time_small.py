@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from fourierflow_amd import _capi, _lib  # noqa: E402
-from fourierflow_amd.engine import _p  # noqa: E402
+from fourierflow_amd._lib import ptr as _p  # noqa: E402
 from fourierflow_amd.modules import FNOFactorized2DBlock  # noqa: E402
 from fourierflow_amd.trainer import FFNOTrainer  # noqa: E402
 
