@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 12
+ABI_VERSION = 13
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -298,6 +298,11 @@ SIGNATURES = {
     "ffno_nudft_supported": (I, [I, I, I]),
     "ffno_nudft_modes": (I, [P, P, P, I, I, I, I, I, I, P]),
     "ffno_nudft_points": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P]),
+    "ffno_nudft_axis_supported": (I, [I, I, I]),
+    "ffno_nudft_axis_modes": (I, [P, P, P, I, I, I, I, I, P]),
+    "ffno_nudft_axis_points": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    "ffno_axis_modes_to_grid": (I, [P, P, I, I, I, I, I, I, P]),
+    "ffno_grid_to_axis_modes": (I, [P, P, I, I, I, I, I, I, P]),
     "ffno_iphi_supported": (I, [I]),
     "ffno_iphi_bwd_ws_floats": (SZ, [I, I, I]),
     "ffno_iphi_fwd": (I, [P, P, P, P, P, P, I, I, I, P]),

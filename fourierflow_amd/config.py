@@ -32,6 +32,7 @@ TARGET_MAP = {
     "fourierflow.modules.FNOMesh2D": "fourierflow_amd.modules.FNOMesh2D",
     "fourierflow.modules.FNOMesh3D": "fourierflow_amd.modules.FNOMesh3D",
     "fourierflow.modules.FNOFactorizedPointCloud2D": "fourierflow_amd.modules.FNOFactorizedPointCloud2D",
+    "fourierflow.modules.FNOFullyFactorizedMesh2D": "fourierflow_amd.modules.FNOFullyFactorizedMesh2D",
     "fourierflow.modules.IPhi": "fourierflow_amd.modules.IPhi",
     "fourierflow.modules.WNLinear": "fourierflow_amd.modules.WNLinear",
     "fourierflow.modules.Normalizer": "fourierflow_amd.modules.Normalizer",

@@ -286,6 +286,8 @@ extern "C" int ffno_fw3d_grad_reduce(const float* partial, float* g1, float* g2,
 
 // the point-cloud F-FNO's non-uniform DFT (entry points ffno_nudft_*) lives in this translation unit
 #include "ffno_pointcloud.h"
+// ... and the per-axis one of the fully factorised point-cloud F-FNO (ffno_nudft_axis_*, ffno_axis_modes_to_grid / ffno_grid_to_axis_modes)
+#include "ffno_pointaxis.h"
 // ... and so do its two per-point networks: IPhi (ffno_iphi_*) and the output head (ffno_pchead_*)
 #include "ffno_iphi.h"
 #include "ffno_pchead.h"

@@ -390,6 +390,197 @@ def point_ifft2d(spec, xi):
     return _PointIFFT2dFn.apply(sr.contiguous(), xi.contiguous())
 
 
+# ---- the per-axis transforms of the fully factorised point-cloud F-FNO (csrc/ffno_pointaxis.h) ------------------------------
+# Spectra are complex64 [B, C, m2 + m1]: the m2 modes of coordinate 0 (the y set, fourier_weight[0]) and then the m1 modes of
+# coordinate 1 (the x set, fourier_weight[1]); the autograd functions work on their view_as_real twins.
+
+def _axis_check(xi, B, N, C, m1, m2):
+    _lib.require_device_tensor(xi, "xi")
+    if xi.dim() != 3 or xi.shape[0] != B or (N is not None and xi.shape[1] != N) or xi.shape[2] != 2:
+        raise ValueError(f"xi: expected [B, N, 2] = [{B}, {'N' if N is None else N}, 2], got {tuple(xi.shape)}")
+    _axis_modes_check(C, m1, m2)
+
+
+def _axis_modes_check(C, m1, m2):
+    if m1 < 1 or m2 < 1 or not _lib.get_lib().ffno_nudft_axis_supported(C, m1, m2):
+        raise ValueError(f"per-axis non-uniform DFT: modes ({m1}, {m2}) outside the compiled set (1..32 each)")
+
+
+def _axis_split(spec, modes2, what):
+    """(m1, m2) of a spectrum [B, C, m2 + m1]; modes2 = None means modes1 = modes2."""
+    if not isinstance(spec, torch.Tensor) or spec.dtype != torch.complex64:
+        raise TypeError(f"{what}: expected a complex64 tensor, got {getattr(spec, 'dtype', type(spec))}")
+    if spec.dim() != 3:
+        raise ValueError(f"{what}: expected [B, C, modes2 + modes1], got {tuple(spec.shape)}")
+    K = spec.shape[2]
+    if modes2 is None:
+        if K % 2:
+            raise ValueError(f"{what}: {K} modes do not split evenly; pass modes2")
+        modes2 = K // 2
+    modes2 = int(modes2)
+    if not 1 <= modes2 < K:
+        raise ValueError(f"{what}: modes2 = {modes2} does not split {K} modes")
+    return K - modes2, modes2
+
+
+def _axis_grid_guard(m1, m2, S, C):
+    if m1 > S // 2 + 1 or m2 > S // 2 + 1:
+        raise ValueError(f"modes ({m1}, {m2}) exceed S // 2 + 1 = {S // 2 + 1} of a {S} x {S} latent grid")
+    if S > 256 or C > 256 or S * C > 8192:
+        raise ValueError(f"latent grid {S} x {S} with {C} channels is outside the compiled set (S <= 256, C <= 256, S C <= 8192)")
+
+
+class _PointAxisFFTFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, xi, m1, m2):
+        B, C, N = u.shape
+        spec = torch.empty(B, C, m1 + m2, 2, dtype=torch.float32, device=u.device)
+        _capi.check(_lib.get_lib().ffno_nudft_axis_modes(_p(u), _p(xi), _p(spec), B, C, N, m1, m2, _lib.current_stream(u.device)),
+                    "nudft_axis_modes")
+        ctx.save_for_backward(u, xi)
+        ctx.cfg = (m1, m2)
+        return spec
+
+    @staticmethod
+    def backward(ctx, gspec):
+        u, xi = ctx.saved_tensors
+        m1, m2 = ctx.cfg
+        B, C, N = u.shape
+        gspec = gspec.contiguous()
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        dxi = torch.empty_like(xi) if ctx.needs_input_grad[1] else None
+        if du is not None or dxi is not None:
+            # the adjoint in u is the modes -> points sum: du = Re sum dY E, and w = u gives dxi in the same launch
+            _capi.check(_lib.get_lib().ffno_nudft_axis_points(_p(gspec), _p(xi), _p(u), _p(du), _p(dxi), B, C, N, m1, m2, 0,
+                                                              _lib.current_stream(u.device)), "nudft_axis_points (adjoint)")
+        return du, dxi, None, None
+
+
+class _PointAxisIFFTFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, xi, m1, m2):
+        B, C = spec.shape[:2]
+        N = xi.shape[1]
+        out = torch.empty(B, C, N, dtype=torch.float32, device=spec.device)
+        _capi.check(_lib.get_lib().ffno_nudft_axis_points(_p(spec), _p(xi), None, _p(out), None, B, C, N, m1, m2, 0,
+                                                          _lib.current_stream(spec.device)), "nudft_axis_points")
+        ctx.save_for_backward(spec, xi)
+        ctx.cfg = (m1, m2)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        spec, xi = ctx.saved_tensors
+        m1, m2 = ctx.cfg
+        B, C = spec.shape[:2]
+        N = xi.shape[1]
+        lib = _lib.get_lib()
+        st = _lib.current_stream(spec.device)
+        gout = gout.contiguous()
+        dspec = dxi = None
+        if ctx.needs_input_grad[0]:
+            dspec = torch.empty_like(spec)
+            _capi.check(lib.ffno_nudft_axis_modes(_p(gout), _p(xi), _p(dspec), B, C, N, m1, m2, st), "nudft_axis_modes (adjoint)")
+        if ctx.needs_input_grad[1]:
+            dxi = torch.empty_like(xi)
+            _capi.check(lib.ffno_nudft_axis_points(_p(spec), _p(xi), _p(gout), None, _p(dxi), B, C, N, m1, m2, 0, st),
+                        "nudft_axis_points (xi gradient)")
+        return dspec, dxi, None, None
+
+
+class _AxisModesToGridFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, S, m1, m2):
+        B, C = spec.shape[:2]
+        out = torch.empty(B, S, S, C, dtype=torch.float32, device=spec.device)
+        _capi.check(_lib.get_lib().ffno_axis_modes_to_grid(_p(spec), _p(out), B, C, S, m1, m2, 1, _lib.current_stream(spec.device)),
+                    "axis_modes_to_grid")
+        ctx.cfg = (S, m1, m2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        S, m1, m2 = ctx.cfg
+        g = g.contiguous()
+        B, C = g.shape[0], g.shape[3]
+        dspec = torch.empty(B, C, m1 + m2, 2, dtype=torch.float32, device=g.device)
+        _capi.check(_lib.get_lib().ffno_grid_to_axis_modes(_p(g), _p(dspec), B, C, S, m1, m2, 1, _lib.current_stream(g.device)),
+                    "grid_to_axis_modes (adjoint)")
+        return dspec, None, None, None
+
+
+class _GridToAxisModesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, m1, m2):
+        B, S, _, C = x.shape
+        spec = torch.empty(B, C, m1 + m2, 2, dtype=torch.float32, device=x.device)
+        _capi.check(_lib.get_lib().ffno_grid_to_axis_modes(_p(x), _p(spec), B, C, S, m1, m2, 0, _lib.current_stream(x.device)),
+                    "grid_to_axis_modes")
+        ctx.cfg = (S, m1, m2)
+        return spec
+
+    @staticmethod
+    def backward(ctx, gspec):
+        S, m1, m2 = ctx.cfg
+        gspec = gspec.contiguous()
+        B, C = gspec.shape[:2]
+        dx = torch.empty(B, S, S, C, dtype=torch.float32, device=gspec.device)
+        _capi.check(_lib.get_lib().ffno_axis_modes_to_grid(_p(gspec), _p(dx), B, C, S, m1, m2, 0, _lib.current_stream(gspec.device)),
+                    "axis_modes_to_grid (adjoint)")
+        return dx, None, None
+
+
+def point_axis_fft(u, xi, modes1: int, modes2: int):
+    """The two "bcn,bnxy->bcxy" einsums of the fully factorised point-cloud SpectralConv2d over its one-dimensional bases
+    (reference modules/factorized_fno/mesh_plus_2d.py:65, :93 with get_fft_bases :118-142): u [B, C, N] on the points xi
+    [B, N, 2] -> complex64 [B, C, modes2 + modes1], sum_n u exp(-2 pi i j xi_0) for j < modes2, then sum_n u exp(-2 pi i k xi_1)
+    for k < modes1.  Differentiable in u and xi."""
+    _lib.require_device_tensor(u, "u")
+    if u.dim() != 3:
+        raise ValueError(f"u: expected [B, C, N], got {tuple(u.shape)}")
+    B, C, N = u.shape
+    _axis_check(xi, B, N, C, int(modes1), int(modes2))
+    return torch.view_as_complex(_PointAxisFFTFn.apply(u.contiguous(), xi.contiguous(), int(modes1), int(modes2)))
+
+
+def point_axis_ifft(spec, xi, modes2=None):
+    """The two "bcxy,bnxy->bcn" einsums over get_ifft_bases and their sum (mesh_plus_2d.py:83-84, :109-110, :114, :144-168) once
+    the repeated grid axis is summed: complex64 spec [B, C, modes2 + modes1] in point_axis_fft's layout -> real [B, C, N] =
+    Re sum_j spec_j exp(2 pi i j xi_0) + Re sum_k spec_{modes2 + k} exp(2 pi i k xi_1), no normalisation.  ``modes2`` = None
+    means modes1 = modes2.  Differentiable in spec and xi."""
+    m1, m2 = _axis_split(spec, modes2, "spec")
+    sr = torch.view_as_real(spec)
+    _lib.require_device_tensor(sr, "spec")
+    B, C = spec.shape[:2]
+    _axis_check(xi, B, None, C, m1, m2)
+    return _PointAxisIFFTFn.apply(sr.contiguous(), xi.contiguous(), m1, m2)
+
+
+def axis_modes_to_grid(spec, S: int, modes2=None):
+    """The x_out = None branch of the fully factorised point-cloud SpectralConv2d after its mix (mesh_plus_2d.py:69-78, :97-106,
+    :114): complex64 spec [B, C, modes2 + modes1] -> channels-last real [B, S, S, C] = h(x) + g(y), g = torch.fft.irfft of the
+    first modes2 modes zero-padded to S // 2 + 1 (n = S), h likewise of the last modes1.  Differentiable in spec."""
+    m1, m2 = _axis_split(spec, modes2, "spec")
+    sr = torch.view_as_real(spec)
+    _lib.require_device_tensor(sr, "spec")
+    _axis_modes_check(spec.shape[1], m1, m2)
+    _axis_grid_guard(m1, m2, int(S), spec.shape[1])
+    return _AxisModesToGridFn.apply(sr.contiguous(), int(S), m1, m2)
+
+
+def grid_to_axis_modes(x, modes1: int, modes2: int):
+    """The x_in = None branch up to its mix when the output lies on points (mesh_plus_2d.py:61, :89 and the sum over the repeated
+    basis axis of :83-84, :109-110): channels-last grid x [B, S, S, C] -> complex64 [B, C, modes2 + modes1], rfft over y of
+    sum_x x truncated to modes2, then rfft over x of sum_y x truncated to modes1.  Differentiable in x."""
+    _lib.require_device_tensor(x, "grid")
+    if x.dim() != 4 or x.shape[1] != x.shape[2]:
+        raise ValueError(f"expected a square channels-last grid [B, S, S, C], got {tuple(x.shape)}")
+    m1, m2 = int(modes1), int(modes2)
+    _axis_modes_check(x.shape[3], m1, m2)
+    _axis_grid_guard(m1, m2, x.shape[1], x.shape[3])
+    return torch.view_as_complex(_GridToAxisModesFn.apply(x.contiguous(), m1, m2))
+
+
 # ---- grid <-> corner modes: the two ends of the point-cloud F-FNO's latent grid (rfft2 / irfft2 restricted to the kept corners) ----
 # Mode-major spectra are the grid kernels' layout: Z[ky][kx'][b][re/im][c], kx' < m1 the rows k1 = kx', kx' >= m1 the rows
 # k1 = kx' - 2 m1; the non-uniform DFT's layout is [b][c][kx'][ky][re/im].  The kernels' twiddle tables carry 1 / sqrt(L) per

@@ -81,8 +81,9 @@ const char* ffno_build_target(void);
  * with; a caller compares it with the FFNO_ABI_VERSION it was compiled against before the first compute call (the Python host
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
  * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
- * in the same way.  12: ffno_ns2d_cn_update_harmonic / ffno_ns2d_harmonic_force, likewise. */
-#define FFNO_ABI_VERSION 12
+ * in the same way.  12: ffno_ns2d_cn_update_harmonic / ffno_ns2d_harmonic_force, likewise.  13: ffno_nudft_axis_* /
+ * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise. */
+#define FFNO_ABI_VERSION 13
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -1161,6 +1162,38 @@ int ffno_nudft_modes(const float* u, const float* xi, float* spec, int B, int C,
                      void* stream);
 int ffno_nudft_points(const float* spec, const float* xi, const float* w, float* out, float* dxi, int B, int C, int N,
                       int m1, int m2, int quirk, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Per-axis non-uniform DFT of FNOFullyFactorizedMesh2D (reference fourierflow/modules/factorized_fno/mesh_plus_2d.py): the
+ * one-dimensional bases of SpectralConv2d.get_fft_bases (:118-142) / .get_ifft_bases (:144-168) and the einsums over them.
+ * Points xi[B][N][2], point features [B][C][N], modes spec[B][C][m2 + m1][2] (= view_as_real of complex64 [B, C, m2 + m1]):
+ * mode t < m2 is wavenumber j = t of coordinate 0 (the y set: modes2, fourier_weight[0], the last grid axis), mode m2 + k is
+ * wavenumber k of coordinate 1 (the x set: modes1, fourier_weight[1], the first grid axis);  E = exp(2 pi i j xi_0) or
+ * exp(2 pi i k xi_1).  The reference repeats each basis along the other grid axis; nothing depends on that axis.
+ *   ffno_nudft_axis_modes:   spec[b][c][t] = sum_n u[b][c][n] conj(E)
+ *       the "bcn,bnxy->bcxy" einsums of :65 and :93 (no normalisation); also d axis_points / d spec applied to dout
+ *   ffno_nudft_axis_points:  out[b][c][n] = Re sum_t spec[b][c][t] E                       (out optional)
+ *       dxi[b][n][d] (+)= sum_c w[b][c][n] d out[b][c][n] / d xi_{n,d}                  (dxi optional, needs w; accumulate: +=)
+ *       the "bcxy,bnxy->bcn" einsums of :83-84 and :109-110 and `xx + xy` (:114) once the repeated axis is summed (see
+ *       ffno_grid_to_axis_modes); also d axis_modes / d u applied to dspec (out = du; w = u gives its dxi), and with w = dout
+ *       the xi gradient of out
+ *   ffno_axis_modes_to_grid: grid[b][x][y][c] = sum_k a_k Re(spec[b][c][m2 + k] e(k x)) + sum_j a_j Re(spec[b][c][j] e(j y)),
+ *       e(j s) = exp(2 pi i j s / S), channels last.  c2r = 1: a = the weights of torch.fft.irfft(zero-padded, n = S) -- 1 / S at
+ *       DC and Nyquist, 2 / S between, imaginary parts of DC and Nyquist ignored: the two irfft of :78 and :106 and their sum
+ *       (:114).  c2r = 0: a = 1, the adjoint of ffno_grid_to_axis_modes(c2r = 0).
+ *   ffno_grid_to_axis_modes: spec[b][c][j] = a_j sum_y (sum_x grid[b][x][y][c]) conj(e(j y)),  spec[b][c][m2 + k] likewise with
+ *       x and y exchanged.  c2r = 0: a = 1, the rfft of :61 / :89 summed over the other grid axis (what the einsums of :83-84 /
+ *       :109-110 do with the repeated basis), truncated to the kept modes.  c2r = 1: the adjoint of
+ *       ffno_axis_modes_to_grid(c2r = 1) (a as there; imaginary parts of DC and Nyquist written as zero).
+ * 1 <= m1, m2 <= 32 (ffno_nudft_axis_supported); the grid entries also need S <= 256, C <= 256, S C <= 8192
+ * (FFNO_EUNSUPPORTED) and m1, m2 <= S / 2 + 1 (FFNO_EMODES).  fp32, deterministic (fixed summation order, no atomics).
+ * --------------------------------------------------------------------------------------------- */
+int ffno_nudft_axis_supported(int C, int m1, int m2);
+int ffno_nudft_axis_modes(const float* u, const float* xi, float* spec, int B, int C, int N, int m1, int m2, void* stream);
+int ffno_nudft_axis_points(const float* spec, const float* xi, const float* w, float* out, float* dxi, int B, int C, int N,
+                           int m1, int m2, int accumulate, void* stream);
+int ffno_axis_modes_to_grid(const float* spec, float* grid, int B, int C, int S, int m1, int m2, int c2r, void* stream);
+int ffno_grid_to_axis_modes(const float* grid, float* spec, int B, int C, int S, int m1, int m2, int c2r, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * IPhi, the coordinate deformation network of the elasticity F-FNO (reference fourierflow/modules/iphi.py:27-58, the
