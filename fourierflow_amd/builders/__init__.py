@@ -4,13 +4,15 @@ device from whole trajectories); and the dataset builders of the mesh and point-
 ``PlasticityBuilder``, ``ElasticityBuilder``: the datasets' own files, split as the reference splits them, held on the device as
 ``DeviceSampleData``), of the torus_li experiments (``NSMarkovBuilder``, ``NSZongyiBuilder``: builders/ns_data.py) and of the
 contextual torus_vis / torus_vis_force experiments (``NSContextualBuilder``: builders/ns_contextual.py) and of the Kolmogorov-flow
-torus_kochkov experiments (``KolmogorovBuilder`` with its two datasets: builders/kolmogorov.py), whose files the Kolmogorov-flow generator writes
+torus_kochkov experiments (``KolmogorovBuilder`` with its two datasets and the multi-resolution training set
+``KolmogorovMultiResolutionDataset`` / ``MultiResolutionMarkovData``: builders/kolmogorov.py), whose files the Kolmogorov-flow generator writes
 (``generate_kolmogorov``, ``KolmogorovStepper``, ``initial_vorticity``: builders/kolmogorov_flow.py).  Without a builder the training commands read ``.npz`` files directly (fourierflow_amd/cli.py)."""
 from .kolmogorov import (KolmogorovBuilder, KolmogorovJAXDataset, KolmogorovJAXTrajectoryDataset,  # noqa: F401
-                         KolmogorovMultiTorchDataset, KolmogorovTorchDataset, KolmogorovTrajectoryDataset)
+                         KolmogorovMultiResolutionDataset, KolmogorovMultiTorchDataset, KolmogorovTorchDataset,
+                         KolmogorovTrajectoryDataset)
 from .kolmogorov_flow import (KolmogorovPlan, KolmogorovStepper, generate_kolmogorov, initial_vorticity,  # noqa: F401
                               plan_kolmogorov, stable_time_step)
-from .markov_data import MarkovTrajectoryData  # noqa: F401
+from .markov_data import MarkovTrajectoryData, MultiResolutionMarkovData  # noqa: F401
 from .mesh_data import ElasticityBuilder, PlasticityBuilder, StructuredMesh2DBuilder  # noqa: F401
 from .ns_contextual import NSContextualBuilder  # noqa: F401
 from .ns_data import NSMarkovBuilder, NSZongyiBuilder  # noqa: F401

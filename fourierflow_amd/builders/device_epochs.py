@@ -86,14 +86,24 @@ class DeviceEpochs:
         for _ in range(n if self.shuffle else 0):
             torch.randperm(self.count, generator=self.gen)
 
-    def epoch(self) -> Iterator[Dict[str, torch.Tensor]]:
+    def _draw(self) -> torch.Tensor:
+        """The ids of the next epoch on the device, in its order: one draw from the permutation stream when shuffled."""
         if self.shuffle:
             self._ids = torch.randperm(self.count, generator=self.gen).to(torch.int32).to(self.device)
         elif self._ids is None:
             self._ids = torch.arange(self.count, dtype=torch.int32).to(self.device)
-        for j in self._mine:
+        return self._ids
+
+    def _slices(self) -> Iterator[tuple]:
+        """(i, offset, B) of this rank's batches of an epoch: its i-th batch reads ids[offset:offset + B]."""
+        for i, j in enumerate(self._mine):
             lo = j * self.batch_size
-            yield self.gather(self._ids, lo, min(self.batch_size, self.count - lo))
+            yield i, lo, min(self.batch_size, self.count - lo)
+
+    def epoch(self) -> Iterator[Dict[str, torch.Tensor]]:
+        ids = self._draw()
+        for _, lo, B in self._slices():
+            yield self.gather(ids, lo, B)
 
     def gather(self, ids: torch.Tensor, offset: int, B: int) -> Dict[str, torch.Tensor]:
         """The batch of the B ids at ids[offset:] (a device int32 array): one launch."""

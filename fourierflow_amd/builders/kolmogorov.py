@@ -15,6 +15,11 @@ Semantics: those of the reference's datasets.
     train   KolmogorovTorchDataset: the pairs x = w[b, ..., t], y = w[b, ..., t + k] for t = 0 ... T - k - 1 (its ``vx`` / ``vy`` items
             are not read by the routine): ``MarkovTrajectoryData`` in mode ``kolmogorov``, one ``ffno_markov_pairs`` launch per
             batch, shuffled, short last batch kept
+    train, several grid sizes   KolmogorovMultiTorchDataset(paths, k, batch_size) (:142-174), built here under the project's own
+            name ``KolmogorovMultiResolutionDataset``: one trajectory file per size, all with the same n and T, every batch drawn
+            from ONE of them in the order ``num_workers`` loader processes would serve them: ``MultiResolutionMarkovData``
+            (builders/markov_data.py has the schedule and its two deviations).  A config selects it with the override
+            ``builder.train_dataset._target_=fourierflow_amd.builders.KolmogorovMultiResolutionDataset``
     valid / test   KolmogorovTrajectoryDataset: with S = slice(None, end, k),
                 data      = concat([initial condition, trajectory], time)[..., S]
                 times     = concat([0.0], time)[S]
@@ -28,20 +33,21 @@ routine compares the last n_steps columns of each; nothing here "aligns" them.)
 
 ``inference_data()`` is the reference's: the joined test trajectories at every k-th time, ``end`` not applied (:60-68).
 
-Not built, and refused by name: ``KolmogorovMultiTorchDataset`` (multi-resolution training), ``KolmogorovJAXDataset`` and
-``KolmogorovJAXTrajectoryDataset`` (the feeds of the ``LearnedInterpolator`` routine, jax-cfd).  ``batch_size`` is used; the other
-loader keywords (``num_workers``, ``pin_memory``, ``loader_target``) are accepted and ignored.
+Not built, and refused by name: ``KolmogorovJAXDataset`` and ``KolmogorovJAXTrajectoryDataset`` (the feeds of the
+``LearnedInterpolator`` routine, jax-cfd) -- and the NAME ``fourierflow.builders.KolmogorovMultiTorchDataset``, which is not mapped to
+the class above yet.  ``batch_size`` is used, ``num_workers`` by the multi-resolution set alone; the other loader
+keywords (``pin_memory``, ``loader_target``) are accepted and ignored.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Union
 
 import numpy as np
 import torch
 
 from .device_epochs import tensor, upload
-from .markov_data import MarkovTrajectoryData
+from .markov_data import MarkovTrajectoryData, MultiResolutionMarkovData
 from .sample_data import DeviceSampleData, Field, broadcast
 
 
@@ -130,6 +136,45 @@ class KolmogorovTorchDataset:
         return w.shape[0] * (w.shape[-1] - self.k)
 
 
+class KolmogorovMultiResolutionDataset:
+    """Paths (one trajectory file per grid size), k and batch size of the training pairs of a multi-resolution run -- the
+    reference's ``KolmogorovMultiTorchDataset(paths, k, batch_size)`` (:142-174) under this project's own name; ``arrays()`` loads
+    every file on first use.  The reference indexes every file with the same ``(b, t)``, so the files agree in n and T; each file's
+    grid may differ from the others'."""
+
+    def __init__(self, paths, k, batch_size):
+        self.paths = [str(p) for p in ([paths] if isinstance(paths, (str, os.PathLike)) else list(paths or []))]
+        self.k, self.batch_size = int(k), int(batch_size)
+        if len(self.paths) < 1:
+            raise ValueError("KolmogorovMultiResolutionDataset: paths names at least one trajectory file, got 0")
+        if self.k < 1:
+            raise ValueError(f"k (the snapshots between input and target) is at least 1, got {k}")
+        if self.batch_size < 1:
+            raise ValueError(f"batch_size is at least 1, got {batch_size}")
+        self._ws: Optional[List[np.ndarray]] = None
+
+    def arrays(self) -> List[np.ndarray]:
+        """w [n, X_s, Y_s, T] of every path, in the order of ``paths``."""
+        if self._ws is None:
+            ws = [load_trajectories(path)[0] for path in self.paths]
+            files = [npz_path(path) for path in self.paths]
+            n, T = ws[0].shape[0], ws[0].shape[-1]
+            for file, w in zip(files[1:], ws[1:]):
+                if (w.shape[0], w.shape[-1]) != (n, T):
+                    raise ValueError(f"{file} holds n = {w.shape[0]} trajectories of T = {w.shape[-1]} snapshots, {files[0]} n = {n} "
+                                     f"of T = {T}: the files of a multi-resolution set are indexed with the same (trajectory, time) "
+                                     f"pairs and must agree in both")
+            if T <= self.k:
+                raise ValueError(f"{', '.join(files)}: trajectories of T = {T} snapshots, a pair k = {self.k} apart needs at least "
+                                 f"{self.k + 1}")
+            self._ws = ws
+        return self._ws
+
+    def __len__(self) -> int:
+        w = self.arrays()[0]
+        return w.shape[0] * (w.shape[-1] - self.k)
+
+
 class KolmogorovTrajectoryDataset:
     """Paths, k and end of a validation / test set; ``arrays()`` loads and joins on first use."""
 
@@ -168,7 +213,10 @@ def _refuse(name: str, why: str):
     return type(name, (), {"__init__": __init__, "__doc__": f"Not built: {why}."})
 
 
-KolmogorovMultiTorchDataset = _refuse("KolmogorovMultiTorchDataset", "training that alternates between several resolutions")
+KolmogorovMultiTorchDataset = _refuse("KolmogorovMultiTorchDataset",
+                                      "training that alternates between several resolutions runs under the name "
+                                      "fourierflow_amd.builders.KolmogorovMultiResolutionDataset (override "
+                                      "builder.train_dataset._target_ with it); this name is not mapped to it yet")
 KolmogorovJAXDataset = _refuse("KolmogorovJAXDataset", "it feeds the LearnedInterpolator routine (jax-cfd), which is not built")
 KolmogorovJAXTrajectoryDataset = _refuse("KolmogorovJAXTrajectoryDataset",
                                          "it feeds the LearnedInterpolator routine (jax-cfd), which is not built")
@@ -178,19 +226,30 @@ class KolmogorovBuilder:
     name = "kolmogorov"
 
     def __init__(self, train_dataset, valid_dataset, test_dataset, loader_target: str = "torch.utils.data.DataLoader", **kwargs):
-        for what, ds, cls in (("train_dataset", train_dataset, KolmogorovTorchDataset),
-                              ("valid_dataset", valid_dataset, KolmogorovTrajectoryDataset),
-                              ("test_dataset", test_dataset, KolmogorovTrajectoryDataset)):
+        for what, ds, cls in (("train_dataset", train_dataset, (KolmogorovTorchDataset, KolmogorovMultiResolutionDataset)),
+                              ("valid_dataset", valid_dataset, (KolmogorovTrajectoryDataset,)),
+                              ("test_dataset", test_dataset, (KolmogorovTrajectoryDataset,))):
             if not isinstance(ds, cls):
-                raise TypeError(f"KolmogorovBuilder: {what} must be a {cls.__name__}, got {type(ds).__name__}")
+                raise TypeError(f"KolmogorovBuilder: {what} must be a {' or a '.join(c.__name__ for c in cls)}, got "
+                                f"{type(ds).__name__}")
         self.train_dataset, self.valid_dataset, self.test_dataset = train_dataset, valid_dataset, test_dataset
         self.kwargs = dict(kwargs)
         self.batch_size = int(self.kwargs.get("batch_size", 1))      # DataLoader's default
+        self.num_workers = int(self.kwargs.get("num_workers", 0))    # (likewise; read by the multi-resolution schedule only)
+        if isinstance(train_dataset, KolmogorovMultiResolutionDataset) and train_dataset.batch_size != self.batch_size:
+            raise ValueError(f"KolmogorovBuilder: train_dataset.batch_size = {train_dataset.batch_size} but the builder's batch_size "
+                             f"= {self.batch_size}: the dataset changes its grid size after every {train_dataset.batch_size} "
+                             f"items, so a batch of {self.batch_size} would hold images of two sizes (set both to the same number)")
 
     def train_data(self, device, seed: int = 0, rank: int = 0, world: int = 1, shuffle: bool = True,
-                   drop_last: bool = False) -> MarkovTrajectoryData:
-        """``train_dataloader()``: ``DataLoader(shuffle=True, drop_last=False)`` over the pairs."""
+                   drop_last: bool = False) -> Union[MarkovTrajectoryData, MultiResolutionMarkovData]:
+        """``train_dataloader()``: ``DataLoader(shuffle=True, drop_last=False)`` over the pairs -- of one file, or of one file per
+        grid size in the order ``num_workers`` loader processes would serve them (builders/markov_data.py)."""
         ds = self.train_dataset
+        if isinstance(ds, KolmogorovMultiResolutionDataset):
+            return MultiResolutionMarkovData(ds.arrays(), device=device, batch_size=self.batch_size, k=ds.k,
+                                             num_workers=self.num_workers, seed=seed, shuffle=shuffle, drop_last=drop_last,
+                                             rank=rank, world=world)
         return MarkovTrajectoryData(ds.arrays(), device=device, batch_size=self.batch_size, mode="kolmogorov", k=ds.k, seed=seed,
                                     shuffle=shuffle, drop_last=drop_last, rank=rank, world=world)
 

@@ -16,11 +16,31 @@ that array, so a step costs no host work beyond the launch.
 
 Order, drop-last and data parallel: the schedule of ``DeviceEpochs`` (builders/device_epochs.py) over the ``n P`` pair ids;
 ``shuffle=False`` is the reference's ``(b t)`` order, p = 0, 1, 2, ...
+
+Several resolutions -- ``MultiResolutionMarkovData``, the counterpart of ``DataLoader(shuffle=True, num_workers=W)`` over
+``KolmogorovMultiTorchDataset`` (builders/kolmogorov.py:142-174).  That dataset opens one file per grid size, indexes every file with
+the same ``(b, t)`` and moves on to the next file after every ``batch_size`` items it has served.  Under a DataLoader with W workers
+
+    every worker copies the dataset, its counter at zero, at the start of every epoch;
+    batch j goes to worker j % W, as that worker's (j // W)-th batch;
+    the worker advances its own file index after every ``batch_size`` items, i.e. after every batch it serves;
+    the one short batch is the epoch's last, so it never shifts a phase
+
+so batch j of an epoch is drawn entirely from file ``(j // W) % len(paths)``, and every epoch starts again at file 0.  Here every
+file's trajectories are uploaded once, an epoch is ONE permutation of the ``n (T - k)`` pair ids shared by all sizes (the schedule
+of ``DeviceEpochs``), and batch i of this rank's epoch is one ``ffno_markov_pairs_tf`` launch in mode ``kolmogorov`` on the array of
+set ``(i // max(1, W)) % len(paths)``: ``x`` and ``y`` only.  Two deviations:
+
+    num_workers = 0   the reference loads in the main process with ONE dataset object, whose counter runs on across epochs (and a
+                      short batch leaves it mid-batch: the next epoch's batches mix two sizes and fail to stack, so this only runs
+                      when n (T - k) is a multiple of the batch size).  Here it behaves as W = 1: every epoch starts at set 0.
+    data parallel     the set index follows the rank's OWN batch position i, not the global batch number j = rank + i world: all
+                      ranks step the same size together (the gradient all-reduce sums like with like).
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict
+from typing import Dict, Iterator, Sequence
 
 import torch
 
@@ -91,3 +111,43 @@ class MarkovTrajectoryData(DeviceEpochs):
                                                  _lib.current_stream(dev))
         _capi.check(rc, "markov_pairs")
         return b
+
+
+class MultiResolutionMarkovData(DeviceEpochs):
+    """``arrays``: one ``data [n, M_s, N_s, T]`` per grid size, all with the same n and T (the same pair ids name the same
+    ``(b, t)`` in every one).  ``num_workers``: the W of the schedule above."""
+
+    def __init__(self, arrays: Sequence, *, device, batch_size: int, k: int = 1, num_workers: int = 0, seed: int,
+                 shuffle: bool = True, drop_last: bool = False, rank: int = 0, world: int = 1):
+        if len(arrays) < 1:
+            raise ValueError("MultiResolutionMarkovData needs the trajectories of at least one grid size, got none")
+        if num_workers < 0:
+            raise ValueError(f"num_workers is at least 0, got {num_workers}")
+        super().__init__(device=device, batch_size=batch_size, seed=seed, shuffle=shuffle, drop_last=drop_last, rank=rank,
+                         world=world)
+        # each size as a single-size set of its own: its array, its checks and its launch (their own schedules are not used)
+        self.sets = [MarkovTrajectoryData(a, device=device, batch_size=batch_size, mode="kolmogorov", k=k, seed=0, shuffle=False)
+                     for a in arrays]
+        first = self.sets[0]
+        for i, s in enumerate(self.sets):
+            if (s.n, s.T) != (first.n, first.T):
+                raise ValueError(f"set {i} holds {s.n} trajectories of {s.T} snapshots, set 0 {first.n} of {first.T}: every "
+                                 f"grid size is indexed with the same (trajectory, time) pairs")
+        self.mode, self.k, self.n, self.T, self.P = "kolmogorov", first.k, first.n, first.T, first.P
+        self.sizes = [(s.M, s.N) for s in self.sets]
+        self.stride = max(1, int(num_workers))      # consecutive batches of one set
+        self.n_pairs = first.n_pairs
+        self._schedule(self.n_pairs, "pairs", first.data)
+
+    def set_index(self, i: int) -> int:
+        """The set that batch i of this rank's epoch is drawn from."""
+        return (i // self.stride) % len(self.sets)
+
+    def epoch(self) -> Iterator[Dict[str, torch.Tensor]]:
+        ids = self._draw()
+        for i, lo, B in self._slices():
+            yield self.sets[self.set_index(i)].gather(ids, lo, B)
+
+    def gather(self, ids: torch.Tensor, offset: int, B: int, set_index: int = 0) -> Dict[str, torch.Tensor]:
+        """The batch of the B ids at ids[offset:] from set `set_index`: one launch."""
+        return self.sets[set_index].gather(ids, offset, B)

@@ -32,7 +32,11 @@ the reference's statistics epoch: one whole pass that only accumulates the norma
 builder's ``inference_data()`` and reports the reference's ``inference_time``; NSContextualBuilder has none, in the reference
 either, and is refused there.  With KolmogorovBuilder the routine reduces its predictions to the grid of ``corr_data`` on the device
 (``downsample_corr``), ``valid_corr`` / ``valid_reduced_time_until`` are the reduced ones, the checkpoint is selected by the config's
-``CustomModelCheckpoint`` entry (``valid_time_until``, max) and `test --builder` also prints ``test_reduced_time_until``.
+``CustomModelCheckpoint`` entry (``valid_time_until``, max) and `test --builder` also prints ``test_reduced_time_until``.  Its
+multi-resolution configs (torus_kochkov/ffno/multi_resolution) take the one override
+``builder.train_dataset._target_=fourierflow_amd.builders.KolmogorovMultiResolutionDataset``: training batches then alternate between
+the grid sizes of ``paths`` in the order the reference's loader workers serve them (builders/markov_data.py), the statistics epoch
+covers both sizes, and validation, test and predict run at the validation files' own size.
 
 ``test CONFIG [--builder | --data TRAJ.npz] [--pred-path P]``: a Markov routine with a ``pred_path`` (the
 torus_kochkov/ffno/predictions configs set ``routine.pred_path``; ``--pred-path`` overrides it) exports every test prediction on its

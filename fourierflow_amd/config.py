@@ -8,7 +8,8 @@ maps ``fourierflow.*`` targets onto their MI355X-native mirrors, so an unmodifie
 the HIP-backed routine.  ``build_routine`` leaves the other sections alone; of them the CLI's ``--builder`` instantiates a
 ``builder`` section that names StructuredMesh2DBuilder, PlasticityBuilder, ElasticityBuilder (builders/mesh_data.py),
 NSMarkovBuilder, NSZongyiBuilder (builders/ns_data.py), NSContextualBuilder (builders/ns_contextual.py) or KolmogorovBuilder with its
-KolmogorovTorchDataset / KolmogorovTrajectoryDataset nodes (builders/kolmogorov.py) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
+KolmogorovTorchDataset / KolmogorovTrajectoryDataset nodes (builders/kolmogorov.py; its multi-resolution training set under the project's
+own target ``fourierflow_amd.builders.KolmogorovMultiResolutionDataset``, an unmapped name that is imported as it stands) and reads ``trainer.max_epochs``; ``callbacks`` / ``wandb`` are parsed but not instantiated (the Lightning control plane is out of
 scope).
 """
 from __future__ import annotations

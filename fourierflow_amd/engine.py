@@ -44,6 +44,11 @@ X3_INTERLEAVE = 3
 FF_WGRAD_ROUNDS = 3
 # workgroups of a Fourier-weight-gradient launch (slices x modes; with per-layer weights slices x modes x layers)
 FW_GRAD_WGS = 512
+# workspaces an engine keeps, one per (batch, grid, saving) geometry, least recently used dropped first.  A run over two grid sizes
+# visits six between two checkpoints -- the full training batch of either size, the short last one, the full and the short
+# validation batch and the test / predict batch -- and must not allocate in the steady state; with four, kept first-in first-out
+# as before, every epoch of such a run dropped and rebuilt its training workspaces.
+WS_CACHE_MAX = 8
 
 
 def _fmix32(h: int) -> int:
@@ -395,7 +400,9 @@ class FFNOEngine(EngineCore):
         self._prep_sig = None       # what _prepare_weights built the derived operands from (None: rebuild)
         self._ws = None             # the current workspace ...
         self._ws_key = None         # ... its key ...
-        self._ws_cache = {}         # ... among a few recent ones: train / validation / rollout batches alternate in a real run
+        # ... among the WS_CACHE_MAX used last: train / validation / rollout batches alternate in a real run, full and short, and a
+        # multi-resolution run (builders/markov_data.py) switches between grid sizes from one optimiser step to the next
+        self._ws_cache = {}
         self._tw: Dict[int, torch.Tensor] = {}      # twiddle tables by axis length
         self._dft_tabs = {}         # DFT-fragment tables by (axis length, modes, direction); False: none for this shape
         self._desc_dev = None       # weight-norm descriptor table ...
@@ -679,7 +686,8 @@ class FFNOEngine(EngineCore):
             return self._ws
         cache = self._ws_cache
         if key in cache:      # (no re-allocation)
-            self._ws, self._ws_key = cache[key], key
+            self._ws, self._ws_key = cache.pop(key), key
+            cache[key] = self._ws      # most recently used last: eviction below takes the one unused for longest
             return self._ws
         lib = _lib.get_lib()
         dev, C, H, L, O = self.device, self.C, self.H, self.L, self.O
@@ -779,7 +787,7 @@ class FFNOEngine(EngineCore):
             ws.red = torch.empty(O * (C + 1), **f32)
         self._ws, self._ws_key = ws, key
         cache[key] = ws
-        while len(cache) > 4:
+        while len(cache) > WS_CACHE_MAX:
             cache.pop(next(iter(cache)))
         return ws
 

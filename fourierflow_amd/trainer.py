@@ -79,6 +79,7 @@ class FFNOTrainer:
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self._gy = None
         self._tmp = None
+        self._loss_bufs = {}           # (gy, tmp) of loss_and_grad by prediction shape
 
     def current_lr(self) -> float:
         """lr used by the NEXT optimiser step (LambdaLR semantics: factor(number of completed steps))."""
@@ -91,8 +92,14 @@ class FFNOTrainer:
         B = pred.shape[0]
         n = pred.numel() // B
         if self._gy is None or self._gy.shape != pred.shape:
-            self._gy = torch.empty_like(pred)
-            self._tmp = torch.empty(int(lib.ffno_lploss_tmp_floats(B, n)), dtype=torch.float32, device=pred.device)
+            # one pair of buffers per prediction shape, kept: a multi-resolution run changes shape from step to step
+            key = tuple(pred.shape)
+            if key not in self._loss_bufs:
+                while len(self._loss_bufs) >= 8:
+                    self._loss_bufs.pop(next(iter(self._loss_bufs)))
+                self._loss_bufs[key] = (torch.empty_like(pred), torch.empty(int(lib.ffno_lploss_tmp_floats(B, n)),
+                                                                            dtype=torch.float32, device=pred.device))
+            self._gy, self._tmp = self._loss_bufs[key]
         if fresh_loss:
             # the kernel writes the loss into a NEW 4-byte tensor (a host-side allocation from the caching allocator, no launch):
             # the caller owns it -- no clone of a persistent buffer afterwards
