@@ -22,17 +22,19 @@ the last grid axis (y, ``modes2``, ``fourier_weight[0]``), coordinate 1 with the
 The reference's `irfft(n=s1, dim=-1)` / `irfft(n=s2, dim=-2)` (:78, :106) mix the two grid axes: it fails for s1 != s2, and so
 does this constructor.  HIP only: CPU tensors raise.
 """
-import numpy as np
 import torch
 import torch.nn as nn
 
-from ... import _lib
+from ... import _lib, ops
+from .._point_cloud import PointCloudLayer, PointCloudModel
 from ..feedforward import FeedForward
 
 
-class SpectralConv2d(nn.Module):
+class SpectralConv2d(PointCloudLayer, nn.Module):
     """mesh_plus_2d.py:14-39: the parameter container of one layer -- ``fourier_weight`` = [modes2 weight, modes1 weight],
     each [in, out, n_modes, 2], and its ``backcast_ff``."""
+
+    model_name = "FNOFullyFactorizedMesh2D"
 
     def __init__(self, in_dim, out_dim, m1, m2, backcast_ff, fourier_weight, factor, ff_weight_norm, n_ff_layers, layer_norm,
                  dropout, s1, s2):
@@ -55,13 +57,11 @@ class SpectralConv2d(nn.Module):
         """complex [in, out, modes2 + modes1]: the y weights, then the x weights"""
         return torch.cat([torch.view_as_complex(self.fourier_weight[0]), torch.view_as_complex(self.fourier_weight[1])], dim=-1)
 
-    def forward(self, *args, **kwargs):
-        raise RuntimeError("the point-cloud Fourier layers run inside FNOFullyFactorizedMesh2D.forward; call the model")
 
+class FNOFullyFactorizedMesh2D(PointCloudModel):
+    iphi_optional = False      # the reference calls iphi unconditionally (mesh_plus_2d.py:123, :149)
 
-class FNOFullyFactorizedMesh2D(nn.Module):
     def __init__(self, modes1, modes2, width, in_channels, out_channels, n_layers=4, is_mesh=True, s1=40, s2=40):
-        super().__init__()
         if s1 != s2:
             raise ValueError(f"FNOFullyFactorizedMesh2D: s1 = {s1} != s2 = {s2}; the reference fails there (its irfft(n=s1, dim=-1) "
                              "mixes the two grid axes), only square latent grids are defined")
@@ -69,68 +69,32 @@ class FNOFullyFactorizedMesh2D(nn.Module):
             raise ValueError(f"FNOFullyFactorizedMesh2D: modes ({modes1}, {modes2}) must lie in 1 .. s1 // 2 + 1 = {s1 // 2 + 1}")
         if n_layers < 1:
             raise ValueError("FNOFullyFactorizedMesh2D: n_layers must be at least 1")
-        self.modes1, self.modes2, self.width, self.is_mesh = modes1, modes2, width, is_mesh
-        self.s1, self.s2, self.n_layers = s1, s2, n_layers
-        self.in_channels, self.out_channels = in_channels, out_channels
-        # registered parameters that forward never reads (PointCloudExperiment keeps those out of the optimiser)
+        super().__init__(modes1, modes2, width, in_channels, out_channels, n_layers, is_mesh, s1, s2)
+        # never used by forward (mesh_plus_2d.py:254-257); kept for state-dict parity
         self.unused_parameter_prefixes = ("ws.", f"convs.{n_layers}.backcast_ff.")
-        self.fc0 = nn.Linear(in_channels, width)
-        self.convs = nn.ModuleList([])
-        self.ws = nn.ModuleList([])
-        self.bs = nn.ModuleList([])
         for _ in range(n_layers + 1):
             self.convs.append(SpectralConv2d(in_dim=width, out_dim=width, m1=modes1, m2=modes2, backcast_ff=None,
                                              fourier_weight=None, factor=2, ff_weight_norm=True, n_ff_layers=2, layer_norm=False,
                                              dropout=0.0, s1=s1, s2=s2))
-        self.bs.append(nn.Conv2d(2, width, 1))
-        self.bs.append(nn.Conv1d(2, width, 1))
-        for _ in range(n_layers - 1):      # never used by forward (mesh_plus_2d.py:254-257); kept for state-dict parity
-            self.ws.append(nn.Conv2d(width, width, 1))
-        self.fc1 = nn.Linear(width, 128)
-        self.fc2 = nn.Linear(128, out_channels)
+        self._register_tail()
 
-    def get_grid(self, shape, device):
-        """[B, s1, s2, 2]: linspace(0, 1, s) per axis, end point included (mesh_plus_2d.py:272-280)."""
-        B, X, Y = shape[0], shape[1], shape[2]
-        gx = torch.tensor(np.linspace(0, 1, X), dtype=torch.float).reshape(1, X, 1, 1).repeat([B, 1, Y, 1])
-        gy = torch.tensor(np.linspace(0, 1, Y), dtype=torch.float).reshape(1, 1, Y, 1).repeat([B, X, 1, 1])
-        return torch.cat((gx, gy), dim=-1).to(device)
-
-    def forward(self, u, code=None, x_in=None, x_out=None, iphi=None):
-        from ... import ops
-        _lib.require_device_tensor(u, "FNOFullyFactorizedMesh2D input")
-        if u.dim() != 3 or u.shape[2] != self.in_channels:
-            raise ValueError(f"expected u [B, N, {self.in_channels}], got {tuple(u.shape)}")
-        if iphi is None:
-            raise ValueError("FNOFullyFactorizedMesh2D needs iphi: the reference calls it unconditionally (mesh_plus_2d.py:123, :149)")
-        if self.is_mesh and x_in is None:
-            x_in = u
-        if self.is_mesh and x_out is None:
-            x_out = u
-        if x_in is None or x_out is None:
-            raise ValueError("is_mesh=False needs explicit x_in and x_out")
-        B, N = u.shape[:2]
-        W, m1, m2, S, L = self.width, self.modes1, self.modes2, self.s1, self.n_layers
-        lib = _lib.get_lib()
+    def _check_kernel_set(self):
+        W, m1, m2 = self.width, self.modes1, self.modes2
         if W not in (32, 64):
             raise ValueError(f"width {W} is outside the compiled channel tiles (32 / 64)")
-        if not lib.ffno_nudft_axis_supported(W, m1, m2):
+        if not _lib.get_lib().ffno_nudft_axis_supported(W, m1, m2):
             raise ValueError(f"modes ({m1}, {m2}) are outside the compiled set of the per-axis non-uniform DFT (1..32 each)")
-        # the reference evaluates iphi in get_fft_bases and again in get_ifft_bases; on the same points that is one evaluation
-        # whose two coordinate gradients autograd sums
-        xi_in = iphi(x_in, code)
-        xi_out = xi_in if x_out is x_in else iphi(x_out, code)
 
-        # layer 0: fc0 is affine in [u, 1], so the transforms of fc0(u) are [fc0.weight | fc0.bias] applied to those of
-        # [u, 1] -- in + 1 channels through the non-uniform DFT instead of W; that mix is folded into the layer's mode weights
-        aug = torch.cat([u.permute(0, 2, 1), torch.ones(B, 1, N, dtype=u.dtype, device=u.device)], dim=1)
+    def forward(self, u, code=None, x_in=None, x_out=None, iphi=None):
+        x_out, xi_in, xi_out = self._points(u, code, x_in, x_out, iphi)
+        m1, m2, S, L = self.modes1, self.modes2, self.s1, self.n_layers
+        # layer 0: the mix of the affine lift is folded into the layer's mode weights
+        aug, w0 = self._lift(u)                                                           # [B, in + 1, N], [W, in + 1]
         a = ops.point_axis_fft(aug, xi_in, m1, m2)                                        # [B, in + 1, m2 + m1]
-        w0 = torch.cat([self.fc0.weight, self.fc0.bias[:, None]], dim=1)                  # [W, in + 1]
         first = self.convs[0]
         folded = torch.einsum("ia,iok->aok", w0.to(torch.complex64), first.mode_weights())
         s = ops.axis_modes_to_grid(torch.einsum("bak,aok->bok", a, folded), S, modes2=m2)  # [B, S, S, W] = h(x) + g(y)
-        grid = self.get_grid([1, S, S], u.device).reshape(S * S, 2)
-        G = ops._LinearFn.apply(grid, self.bs[0].weight.reshape(W, 2).contiguous(), self.bs[0].bias).view(1, S, S, W)
+        G = self._grid_bias(u.device)
         ff = first.backcast_ff
         uc = ops.feedforward(s, None, ff.layers[0][0], ff.layers[1][0]) + G              # no residual in this layer
         mm = max(m1, m2)
@@ -142,4 +106,4 @@ class FNOFullyFactorizedMesh2D(nn.Module):
             uc = ops.feedforward(ops.spectral_conv2d(uc, w_y, w_x, mm), uc, ff.layers[0][0], ff.layers[1][0]) + G
         T = torch.einsum("bik,iok->bok", ops.grid_to_axis_modes(uc, m1, m2), self.convs[L].mode_weights())
         t = ops.point_axis_ifft(T, xi_out, modes2=m2)                                     # [B, W, N]
-        return ops.point_head(t, x_out, self.bs[1], self.fc1, self.fc2)
+        return self._head(t, x_out)

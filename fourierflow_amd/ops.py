@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import functools
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -170,6 +171,23 @@ class _LinearFn(torch.autograd.Function):
         return dx, dW, db
 
 
+@functools.lru_cache(maxsize=32)
+def _zero_bias(n, device):
+    """The bias of a linear without one: the C ABI documents no null bias for ffno_plin_fwd.  Read only, so one per (n, device)."""
+    with torch.inference_mode(False):
+        return torch.zeros(n, dtype=torch.float32, device=device)
+
+
+def linear(rows, W, b=None):
+    """y = rows W^T + b: rows [P, Cin], W [Cout, Cin], b [Cout] or None -> [P, Cout].  Differentiable in all three."""
+    _lib.require_device_tensor(rows, "linear input")
+    if rows.dim() != 2 or W.dim() != 2 or rows.shape[1] != W.shape[1]:
+        raise ValueError(f"expected rows [P, Cin] and W [Cout, Cin], got {tuple(rows.shape)} and {tuple(W.shape)}")
+    if not _lib.get_lib().ffno_plin_supported(W.shape[1], W.shape[0]):
+        raise ValueError(f"linear {W.shape[1]} -> {W.shape[0]} is outside the pointwise-linear kernel set (both widths <= 128)")
+    return _LinearFn.apply(rows.contiguous(), W.contiguous(), _zero_bias(W.shape[0], rows.device) if b is None else b)
+
+
 def wn_linear(x, lin):
     """``WNLinear.forward`` (reference linear.py:41-52 = nn.Linear with weight_norm): x [..., in] -> [..., out]."""
     _lib.require_device_tensor(x, "WNLinear input")
@@ -178,8 +196,7 @@ def wn_linear(x, lin):
     if not _lib.get_lib().ffno_plin_supported(lin.in_features, lin.out_features):
         raise NotImplementedError(f"stand-alone WNLinear({lin.in_features}, {lin.out_features}) is outside the pointwise-linear "
                                   "kernel set (both widths <= 128); inside the F-FNO block the linears run in the fused kernels")
-    W = weight_norm_weight(lin)
-    y = _LinearFn.apply(x.reshape(-1, lin.in_features).contiguous(), W.contiguous(), lin.bias)
+    y = linear(x.reshape(-1, lin.in_features), weight_norm_weight(lin), lin.bias)
     return y.view(*x.shape[:-1], lin.out_features)
 
 
@@ -297,108 +314,25 @@ def lp_rel_loss(pred, target):
     return _LpRelLossFn.apply(pred.contiguous(), target.contiguous())
 
 
-def _nudft_check(xi, B, N, C, m1, m2):
-    _lib.require_device_tensor(xi, "xi")
-    if xi.dim() != 3 or xi.shape[0] != B or xi.shape[1] != N or xi.shape[2] != 2:
-        raise ValueError(f"xi: expected [B, N, 2] = [{B}, {N}, 2], got {tuple(xi.shape)}")
-    if not _lib.get_lib().ffno_nudft_supported(C, m1, m2):
-        raise ValueError(f"non-uniform DFT: modes ({m1}, {m2}) outside the compiled set (1..16 each)")
+def _complex64(t, ndim, what, rank_error=ValueError):
+    """The view_as_real twin of a complex64 tensor of rank ``ndim``; ``what`` names it and its layout in the refusal."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.complex64:
+        raise TypeError(f"{what}: expected a complex64 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != ndim:
+        raise rank_error(f"{what}: expected rank {ndim}, got {tuple(t.shape)}")
+    return torch.view_as_real(t)
 
 
-class _PointFFT2dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, xi, m1, m2):
-        lib = _lib.get_lib()
-        B, C, N = u.shape
-        spec = torch.empty(B, C, 2 * m1, m2, 2, dtype=torch.float32, device=u.device)
-        _capi.check(lib.ffno_nudft_modes(_p(u), _p(xi), _p(spec), B, C, N, m1, m2, 0, _lib.current_stream(u.device)),
-                    "nudft_modes")
-        ctx.save_for_backward(u, xi)
-        ctx.cfg = (m1, m2)
-        return spec
-
-    @staticmethod
-    def backward(ctx, gspec):
-        u, xi = ctx.saved_tensors
-        m1, m2 = ctx.cfg
-        B, C, N = u.shape
-        gspec = gspec.contiguous()
-        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
-        dxi = torch.empty_like(xi) if ctx.needs_input_grad[1] else None
-        if du is not None or dxi is not None:
-            # the adjoint of fft2d is the modes -> points sum without the ifft2d factor: du = Re sum dY E, dxi from w = u
-            _capi.check(_lib.get_lib().ffno_nudft_points(_p(gspec), _p(xi), _p(u), _p(du), _p(dxi), B, C, N, m1, m2, 0, 0,
-                                                         _lib.current_stream(u.device)), "nudft_points (fft2d adjoint)")
-        return du, dxi, None, None
-
-
-class _PointIFFT2dFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, spec, xi):
-        lib = _lib.get_lib()
-        B, C, R, m2, _ = spec.shape
-        N = xi.shape[1]
-        out = torch.empty(B, C, N, dtype=torch.float32, device=spec.device)
-        _capi.check(lib.ffno_nudft_points(_p(spec), _p(xi), None, _p(out), None, B, C, N, R // 2, m2, 1, 0,
-                                          _lib.current_stream(spec.device)), "nudft_points")
-        ctx.save_for_backward(spec, xi)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        spec, xi = ctx.saved_tensors
-        B, C, R, m2, _ = spec.shape
-        N = xi.shape[1]
-        lib = _lib.get_lib()
-        st = _lib.current_stream(spec.device)
-        gout = gout.contiguous()
-        dspec = dxi = None
-        if ctx.needs_input_grad[0]:
-            dspec = torch.empty_like(spec)
-            _capi.check(lib.ffno_nudft_modes(_p(gout), _p(xi), _p(dspec), B, C, N, R // 2, m2, 1, st), "nudft_modes (ifft2d adjoint)")
-        if ctx.needs_input_grad[1]:
-            dxi = torch.empty_like(xi)
-            _capi.check(lib.ffno_nudft_points(_p(spec), _p(xi), _p(gout), None, _p(dxi), B, C, N, R // 2, m2, 1, 0, st),
-                        "nudft_points (ifft2d xi gradient)")
-        return dspec, dxi
-
-
-def point_fft2d(u, xi, modes1: int, modes2: int):
-    """``SpectralConv2d.fft2d(u, x_in)`` of the point-cloud F-FNO followed by its corner slicing (reference
-    modules/factorized_fno/point_cloud_2d.py:95-131, :54-62): u [B, C, N] on the points xi [B, N, 2] -> complex64
-    [B, C, 2 modes1, modes2], rows k1 = 0..modes1-1 then -modes1..-1, columns k2 = 0..modes2-1.  Differentiable in u and xi."""
-    _lib.require_device_tensor(u, "u")
-    if u.dim() != 3:
-        raise ValueError(f"u: expected [B, C, N], got {tuple(u.shape)}")
-    B, C, N = u.shape
-    _nudft_check(xi, B, N, C, modes1, modes2)
-    return torch.view_as_complex(_PointFFT2dFn.apply(u.contiguous(), xi.contiguous(), int(modes1), int(modes2)))
-
-
-def point_ifft2d(spec, xi):
-    """``SpectralConv2d.ifft2d(spec, x_out)`` of the point-cloud F-FNO (reference point_cloud_2d.py:133-159): complex64 spec
-    [B, C, 2 m1, m2] in the layout point_fft2d returns -> real [B, C, N] on the points xi [B, N, 2], including the reference's
-    `flip(-1, -2).conj()` completion of the negative-k2 half exactly as it computes it.  Differentiable in spec and xi."""
-    if not isinstance(spec, torch.Tensor) or spec.dtype != torch.complex64:
-        raise TypeError(f"spec: expected a complex64 tensor, got {getattr(spec, 'dtype', type(spec))}")
-    if spec.dim() != 4 or spec.shape[2] % 2:
-        raise ValueError(f"spec: expected [B, C, 2 m1, m2], got {tuple(spec.shape)}")
-    sr = torch.view_as_real(spec)
-    _lib.require_device_tensor(sr, "spec")
-    B, C, R, m2 = spec.shape
-    _nudft_check(xi, B, xi.shape[1] if xi.dim() == 3 else -1, C, R // 2, m2)
-    return _PointIFFT2dFn.apply(sr.contiguous(), xi.contiguous())
-
-
-# ---- the per-axis transforms of the fully factorised point-cloud F-FNO (csrc/ffno_pointaxis.h) ------------------------------
-# Spectra are complex64 [B, C, m2 + m1]: the m2 modes of coordinate 0 (the y set, fourier_weight[0]) and then the m1 modes of
-# coordinate 1 (the x set, fourier_weight[1]); the autograd functions work on their view_as_real twins.
-
-def _axis_check(xi, B, N, C, m1, m2):
+def _check_xi(xi, B, N=None):
+    """xi is a device tensor [B, N, 2]; N = None: any number of points."""
     _lib.require_device_tensor(xi, "xi")
     if xi.dim() != 3 or xi.shape[0] != B or (N is not None and xi.shape[1] != N) or xi.shape[2] != 2:
         raise ValueError(f"xi: expected [B, N, 2] = [{B}, {'N' if N is None else N}, 2], got {tuple(xi.shape)}")
-    _axis_modes_check(C, m1, m2)
+
+
+def _corner_modes_check(C, m1, m2):
+    if not _lib.get_lib().ffno_nudft_supported(C, m1, m2):
+        raise ValueError(f"non-uniform DFT: modes ({m1}, {m2}) outside the compiled set (1..16 each)")
 
 
 def _axis_modes_check(C, m1, m2):
@@ -406,12 +340,123 @@ def _axis_modes_check(C, m1, m2):
         raise ValueError(f"per-axis non-uniform DFT: modes ({m1}, {m2}) outside the compiled set (1..32 each)")
 
 
+class _PointTransform(NamedTuple):
+    """One points <-> modes transform of the C ABI: its points -> modes and modes -> points entry points, each with the trailing
+    flags this transform fixes, the real spectrum's shape after [B, C] for (m1, m2), and its name in a failed launch's message."""
+    tag: str
+    modes: str
+    modes_flags: tuple
+    points: str
+    points_flags: tuple
+    spec_shape: Callable
+
+    def to_modes(self, u, xi, spec, dims, what=""):
+        """spec = sum_n u E(xi); dims = (B, C, N, m1, m2)"""
+        _capi.check(getattr(_lib.get_lib(), self.modes)(_p(u), _p(xi), _p(spec), *dims, *self.modes_flags,
+                                                        _lib.current_stream(u.device)), self.modes[5:] + what)
+
+    def to_points(self, spec, xi, w, out, dxi, dims, what=""):
+        """out = Re sum_k spec E(xi) (when given) and dxi = its coordinate gradient weighted with w (when given)"""
+        _capi.check(getattr(_lib.get_lib(), self.points)(_p(spec), _p(xi), _p(w), _p(out), _p(dxi), *dims, *self.points_flags,
+                                                         _lib.current_stream(spec.device)), self.points[5:] + what)
+
+
+# fft2d and its corner slicing / ifft2d with the reference's completion of the negative-k2 half: spectra [B, C, 2 m1, m2]
+_FFT2D = _PointTransform("fft2d ", "ffno_nudft_modes", (0,), "ffno_nudft_points", (0, 0), lambda m1, m2: (2 * m1, m2, 2))
+_IFFT2D = _PointTransform("ifft2d ", "ffno_nudft_modes", (1,), "ffno_nudft_points", (1, 0), lambda m1, m2: (2 * m1, m2, 2))
+# the per-axis transforms of the fully factorised point-cloud F-FNO (csrc/ffno_pointaxis.h).  Spectra are complex64
+# [B, C, m2 + m1]: the m2 modes of coordinate 0 (the y set, fourier_weight[0]) and then the m1 modes of coordinate 1 (the x set,
+# fourier_weight[1]); the autograd functions work on their view_as_real twins.
+_AXIS = _PointTransform("", "ffno_nudft_axis_modes", (), "ffno_nudft_axis_points", (0,), lambda m1, m2: (m1 + m2, 2))
+
+
+class _PointsToModesFn(torch.autograd.Function):
+    """u [B, C, N] on the points xi -> the real twin of the spectrum of transform ``tr``."""
+
+    @staticmethod
+    def forward(ctx, u, xi, tr, m1, m2):
+        B, C, N = u.shape
+        spec = torch.empty(B, C, *tr.spec_shape(m1, m2), dtype=torch.float32, device=u.device)
+        tr.to_modes(u, xi, spec, (B, C, N, m1, m2))
+        ctx.save_for_backward(u, xi)
+        ctx.cfg = (tr, m1, m2)
+        return spec
+
+    @staticmethod
+    def backward(ctx, gspec):
+        u, xi = ctx.saved_tensors
+        tr, m1, m2 = ctx.cfg
+        gspec = gspec.contiguous()
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
+        dxi = torch.empty_like(xi) if ctx.needs_input_grad[1] else None
+        if du is not None or dxi is not None:
+            # the adjoint in u is the modes -> points sum without any inverse factor: du = Re sum dY E, and w = u gives dxi in
+            # the same launch
+            tr.to_points(gspec, xi, u, du, dxi, (*u.shape, m1, m2), f" ({tr.tag}adjoint)")
+        return du, dxi, None, None, None
+
+
+class _ModesToPointsFn(torch.autograd.Function):
+    """The real twin of a spectrum of transform ``tr`` -> real [B, C, N] on the points xi."""
+
+    @staticmethod
+    def forward(ctx, spec, xi, tr, m1, m2):
+        B, C = spec.shape[:2]
+        N = xi.shape[1]
+        out = torch.empty(B, C, N, dtype=torch.float32, device=spec.device)
+        tr.to_points(spec, xi, None, out, None, (B, C, N, m1, m2))
+        ctx.save_for_backward(spec, xi)
+        ctx.cfg = (tr, m1, m2)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        spec, xi = ctx.saved_tensors
+        tr, m1, m2 = ctx.cfg
+        dims = (spec.shape[0], spec.shape[1], xi.shape[1], m1, m2)
+        gout = gout.contiguous()
+        dspec = dxi = None
+        if ctx.needs_input_grad[0]:
+            dspec = torch.empty_like(spec)
+            tr.to_modes(gout, xi, dspec, dims, f" ({tr.tag}adjoint)")
+        if ctx.needs_input_grad[1]:
+            dxi = torch.empty_like(xi)
+            tr.to_points(spec, xi, gout, None, dxi, dims, f" ({tr.tag}xi gradient)")
+        return dspec, dxi, None, None, None
+
+
+def _check_points(u, xi):
+    _lib.require_device_tensor(u, "u")
+    if u.dim() != 3:
+        raise ValueError(f"u: expected [B, C, N], got {tuple(u.shape)}")
+    _check_xi(xi, u.shape[0], u.shape[2])
+
+
+def point_fft2d(u, xi, modes1: int, modes2: int):
+    """``SpectralConv2d.fft2d(u, x_in)`` of the point-cloud F-FNO followed by its corner slicing (reference
+    modules/factorized_fno/point_cloud_2d.py:95-131, :54-62): u [B, C, N] on the points xi [B, N, 2] -> complex64
+    [B, C, 2 modes1, modes2], rows k1 = 0..modes1-1 then -modes1..-1, columns k2 = 0..modes2-1.  Differentiable in u and xi."""
+    _check_points(u, xi)
+    _corner_modes_check(u.shape[1], modes1, modes2)
+    return torch.view_as_complex(_PointsToModesFn.apply(u.contiguous(), xi.contiguous(), _FFT2D, int(modes1), int(modes2)))
+
+
+def point_ifft2d(spec, xi):
+    """``SpectralConv2d.ifft2d(spec, x_out)`` of the point-cloud F-FNO (reference point_cloud_2d.py:133-159): complex64 spec
+    [B, C, 2 m1, m2] in the layout point_fft2d returns -> real [B, C, N] on the points xi [B, N, 2], including the reference's
+    `flip(-1, -2).conj()` completion of the negative-k2 half exactly as it computes it.  Differentiable in spec and xi."""
+    sr = _complex64(spec, 4, "spec [B, C, 2 m1, m2]")
+    if spec.shape[2] % 2:
+        raise ValueError(f"spec: expected [B, C, 2 m1, m2], got {tuple(spec.shape)}")
+    _lib.require_device_tensor(sr, "spec")
+    B, C, R, m2 = spec.shape
+    _check_xi(xi, B)
+    _corner_modes_check(C, R // 2, m2)
+    return _ModesToPointsFn.apply(sr.contiguous(), xi.contiguous(), _IFFT2D, R // 2, m2)
+
+
 def _axis_split(spec, modes2, what):
     """(m1, m2) of a spectrum [B, C, m2 + m1]; modes2 = None means modes1 = modes2."""
-    if not isinstance(spec, torch.Tensor) or spec.dtype != torch.complex64:
-        raise TypeError(f"{what}: expected a complex64 tensor, got {getattr(spec, 'dtype', type(spec))}")
-    if spec.dim() != 3:
-        raise ValueError(f"{what}: expected [B, C, modes2 + modes1], got {tuple(spec.shape)}")
     K = spec.shape[2]
     if modes2 is None:
         if K % 2:
@@ -430,104 +475,30 @@ def _axis_grid_guard(m1, m2, S, C):
         raise ValueError(f"latent grid {S} x {S} with {C} channels is outside the compiled set (S <= 256, C <= 256, S C <= 8192)")
 
 
-class _PointAxisFFTFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, u, xi, m1, m2):
-        B, C, N = u.shape
-        spec = torch.empty(B, C, m1 + m2, 2, dtype=torch.float32, device=u.device)
-        _capi.check(_lib.get_lib().ffno_nudft_axis_modes(_p(u), _p(xi), _p(spec), B, C, N, m1, m2, _lib.current_stream(u.device)),
-                    "nudft_axis_modes")
-        ctx.save_for_backward(u, xi)
-        ctx.cfg = (m1, m2)
-        return spec
+class _AxisGridFn(torch.autograd.Function):
+    """``to_grid``: the real twin of a spectrum [B, C, m2 + m1] -> channels-last grid [B, S, S, C]; otherwise the grid -> the
+    spectrum.  The two kernels are each other's adjoint under the same ``c2r`` flag: 1 around the irfft (spectrum -> grid
+    forward), 0 around the rfft (grid -> spectrum forward)."""
 
     @staticmethod
-    def backward(ctx, gspec):
-        u, xi = ctx.saved_tensors
-        m1, m2 = ctx.cfg
-        B, C, N = u.shape
-        gspec = gspec.contiguous()
-        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None
-        dxi = torch.empty_like(xi) if ctx.needs_input_grad[1] else None
-        if du is not None or dxi is not None:
-            # the adjoint in u is the modes -> points sum: du = Re sum dY E, and w = u gives dxi in the same launch
-            _capi.check(_lib.get_lib().ffno_nudft_axis_points(_p(gspec), _p(xi), _p(u), _p(du), _p(dxi), B, C, N, m1, m2, 0,
-                                                              _lib.current_stream(u.device)), "nudft_axis_points (adjoint)")
-        return du, dxi, None, None
-
-
-class _PointAxisIFFTFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, spec, xi, m1, m2):
-        B, C = spec.shape[:2]
-        N = xi.shape[1]
-        out = torch.empty(B, C, N, dtype=torch.float32, device=spec.device)
-        _capi.check(_lib.get_lib().ffno_nudft_axis_points(_p(spec), _p(xi), None, _p(out), None, B, C, N, m1, m2, 0,
-                                                          _lib.current_stream(spec.device)), "nudft_axis_points")
-        ctx.save_for_backward(spec, xi)
-        ctx.cfg = (m1, m2)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        spec, xi = ctx.saved_tensors
-        m1, m2 = ctx.cfg
-        B, C = spec.shape[:2]
-        N = xi.shape[1]
+    def _run(t, S, m1, m2, to_grid, c2r, what):
+        B, C = (t.shape[0], t.shape[1]) if to_grid else (t.shape[0], t.shape[3])
+        out = torch.empty((B, S, S, C) if to_grid else (B, C, m1 + m2, 2), dtype=torch.float32, device=t.device)
         lib = _lib.get_lib()
-        st = _lib.current_stream(spec.device)
-        gout = gout.contiguous()
-        dspec = dxi = None
-        if ctx.needs_input_grad[0]:
-            dspec = torch.empty_like(spec)
-            _capi.check(lib.ffno_nudft_axis_modes(_p(gout), _p(xi), _p(dspec), B, C, N, m1, m2, st), "nudft_axis_modes (adjoint)")
-        if ctx.needs_input_grad[1]:
-            dxi = torch.empty_like(xi)
-            _capi.check(lib.ffno_nudft_axis_points(_p(spec), _p(xi), _p(gout), None, _p(dxi), B, C, N, m1, m2, 0, st),
-                        "nudft_axis_points (xi gradient)")
-        return dspec, dxi, None, None
-
-
-class _AxisModesToGridFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, spec, S, m1, m2):
-        B, C = spec.shape[:2]
-        out = torch.empty(B, S, S, C, dtype=torch.float32, device=spec.device)
-        _capi.check(_lib.get_lib().ffno_axis_modes_to_grid(_p(spec), _p(out), B, C, S, m1, m2, 1, _lib.current_stream(spec.device)),
-                    "axis_modes_to_grid")
-        ctx.cfg = (S, m1, m2)
+        fn = lib.ffno_axis_modes_to_grid if to_grid else lib.ffno_grid_to_axis_modes
+        _capi.check(fn(_p(t), _p(out), B, C, S, m1, m2, c2r, _lib.current_stream(t.device)), what)
         return out
+
+    @staticmethod
+    def forward(ctx, t, S, m1, m2, to_grid):
+        ctx.cfg = (S, m1, m2, to_grid)
+        return _AxisGridFn._run(t, S, m1, m2, to_grid, int(to_grid), "axis_modes_to_grid" if to_grid else "grid_to_axis_modes")
 
     @staticmethod
     def backward(ctx, g):
-        S, m1, m2 = ctx.cfg
-        g = g.contiguous()
-        B, C = g.shape[0], g.shape[3]
-        dspec = torch.empty(B, C, m1 + m2, 2, dtype=torch.float32, device=g.device)
-        _capi.check(_lib.get_lib().ffno_grid_to_axis_modes(_p(g), _p(dspec), B, C, S, m1, m2, 1, _lib.current_stream(g.device)),
-                    "grid_to_axis_modes (adjoint)")
-        return dspec, None, None, None
-
-
-class _GridToAxisModesFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, m1, m2):
-        B, S, _, C = x.shape
-        spec = torch.empty(B, C, m1 + m2, 2, dtype=torch.float32, device=x.device)
-        _capi.check(_lib.get_lib().ffno_grid_to_axis_modes(_p(x), _p(spec), B, C, S, m1, m2, 0, _lib.current_stream(x.device)),
-                    "grid_to_axis_modes")
-        ctx.cfg = (S, m1, m2)
-        return spec
-
-    @staticmethod
-    def backward(ctx, gspec):
-        S, m1, m2 = ctx.cfg
-        gspec = gspec.contiguous()
-        B, C = gspec.shape[:2]
-        dx = torch.empty(B, S, S, C, dtype=torch.float32, device=gspec.device)
-        _capi.check(_lib.get_lib().ffno_axis_modes_to_grid(_p(gspec), _p(dx), B, C, S, m1, m2, 0, _lib.current_stream(gspec.device)),
-                    "axis_modes_to_grid (adjoint)")
-        return dx, None, None
+        S, m1, m2, to_grid = ctx.cfg
+        what = "grid_to_axis_modes (adjoint)" if to_grid else "axis_modes_to_grid (adjoint)"
+        return _AxisGridFn._run(g.contiguous(), S, m1, m2, not to_grid, int(to_grid), what), None, None, None, None
 
 
 def point_axis_fft(u, xi, modes1: int, modes2: int):
@@ -535,12 +506,9 @@ def point_axis_fft(u, xi, modes1: int, modes2: int):
     (reference modules/factorized_fno/mesh_plus_2d.py:65, :93 with get_fft_bases :118-142): u [B, C, N] on the points xi
     [B, N, 2] -> complex64 [B, C, modes2 + modes1], sum_n u exp(-2 pi i j xi_0) for j < modes2, then sum_n u exp(-2 pi i k xi_1)
     for k < modes1.  Differentiable in u and xi."""
-    _lib.require_device_tensor(u, "u")
-    if u.dim() != 3:
-        raise ValueError(f"u: expected [B, C, N], got {tuple(u.shape)}")
-    B, C, N = u.shape
-    _axis_check(xi, B, N, C, int(modes1), int(modes2))
-    return torch.view_as_complex(_PointAxisFFTFn.apply(u.contiguous(), xi.contiguous(), int(modes1), int(modes2)))
+    _check_points(u, xi)
+    _axis_modes_check(u.shape[1], int(modes1), int(modes2))
+    return torch.view_as_complex(_PointsToModesFn.apply(u.contiguous(), xi.contiguous(), _AXIS, int(modes1), int(modes2)))
 
 
 def point_axis_ifft(spec, xi, modes2=None):
@@ -548,24 +516,25 @@ def point_axis_ifft(spec, xi, modes2=None):
     the repeated grid axis is summed: complex64 spec [B, C, modes2 + modes1] in point_axis_fft's layout -> real [B, C, N] =
     Re sum_j spec_j exp(2 pi i j xi_0) + Re sum_k spec_{modes2 + k} exp(2 pi i k xi_1), no normalisation.  ``modes2`` = None
     means modes1 = modes2.  Differentiable in spec and xi."""
+    sr = _complex64(spec, 3, "spec [B, C, modes2 + modes1]")
     m1, m2 = _axis_split(spec, modes2, "spec")
-    sr = torch.view_as_real(spec)
     _lib.require_device_tensor(sr, "spec")
     B, C = spec.shape[:2]
-    _axis_check(xi, B, None, C, m1, m2)
-    return _PointAxisIFFTFn.apply(sr.contiguous(), xi.contiguous(), m1, m2)
+    _check_xi(xi, B)
+    _axis_modes_check(C, m1, m2)
+    return _ModesToPointsFn.apply(sr.contiguous(), xi.contiguous(), _AXIS, m1, m2)
 
 
 def axis_modes_to_grid(spec, S: int, modes2=None):
     """The x_out = None branch of the fully factorised point-cloud SpectralConv2d after its mix (mesh_plus_2d.py:69-78, :97-106,
     :114): complex64 spec [B, C, modes2 + modes1] -> channels-last real [B, S, S, C] = h(x) + g(y), g = torch.fft.irfft of the
     first modes2 modes zero-padded to S // 2 + 1 (n = S), h likewise of the last modes1.  Differentiable in spec."""
+    sr = _complex64(spec, 3, "spec [B, C, modes2 + modes1]")
     m1, m2 = _axis_split(spec, modes2, "spec")
-    sr = torch.view_as_real(spec)
     _lib.require_device_tensor(sr, "spec")
     _axis_modes_check(spec.shape[1], m1, m2)
     _axis_grid_guard(m1, m2, int(S), spec.shape[1])
-    return _AxisModesToGridFn.apply(sr.contiguous(), int(S), m1, m2)
+    return _AxisGridFn.apply(sr.contiguous(), int(S), m1, m2, True)
 
 
 def grid_to_axis_modes(x, modes1: int, modes2: int):
@@ -578,7 +547,7 @@ def grid_to_axis_modes(x, modes1: int, modes2: int):
     m1, m2 = int(modes1), int(modes2)
     _axis_modes_check(x.shape[3], m1, m2)
     _axis_grid_guard(m1, m2, x.shape[1], x.shape[3])
-    return torch.view_as_complex(_GridToAxisModesFn.apply(x.contiguous(), m1, m2))
+    return torch.view_as_complex(_AxisGridFn.apply(x.contiguous(), x.shape[1], m1, m2, False))
 
 
 # ---- grid <-> corner modes: the two ends of the point-cloud F-FNO's latent grid (rfft2 / irfft2 restricted to the kept corners) ----
@@ -640,20 +609,39 @@ class _ModesToGridFn(torch.autograd.Function):
         return dz * (1.0 / float(np.sqrt(ch.Sp[0] * ch.Sp[1]))), None, None
 
 
+def _pack_corner_weights(ch, w1, w2, st):
+    """The two corner weight tensors ([C, C, m1, m2, 2] each) packed for ch.mix -> (the set of the forward mix `bixy,ioxy->boxy`,
+    the transposed set of its adjoint)."""
+    f32 = dict(dtype=torch.float32, device=w1.device)
+    wp, wpt = torch.empty(ch.planes_floats, **f32), torch.empty(ch.planes_floats, **f32)
+    _capi.check(_lib.get_lib().ffno_fw2d_pack2(_p(w1), _p(w2), _p(wp), _p(wpt), ch.C, *ch.Ks, st), "fw2d_pack2")
+    return wp, wpt
+
+
+def _corner_weight_grads(ch, z, dy, st):
+    """The gradients of the two corner weight tensors from the mix's input z and output gradient dy: per-workgroup partial sums,
+    then one fixed-order reduction."""
+    f32 = dict(dtype=torch.float32, device=dy.device)
+    (m1, m2), C = ch.Ks, ch.C
+    part = torch.empty(ch.planes_floats, **f32)
+    gw1, gw2 = torch.empty(C, C, m1, m2, 2, **f32), torch.empty(C, C, m1, m2, 2, **f32)
+    ch.fw_grad_partial(z, dy, part, st)
+    _capi.check(_lib.get_lib().ffno_fw2d_grad_reduce2(_p(part), _p(gw1), _p(gw2), C, m1, m2, 1, 0, st), "fw2d_grad_reduce2")
+    return gw1, gw2
+
+
 class _GridToMixedModesFn(torch.autograd.Function):
     """Channels-last grid [B, s1, s2, C] -> mode-major corners of rfft2 mixed with the two corner weight tensors
     ([C, C, m1, m2, 2] each, `bixy,ioxy->boxy`): [m2, 2 m1, B, 2, C]."""
 
     @staticmethod
     def forward(ctx, x, w1, w2):
-        lib = _lib.get_lib()
         B, s1, s2, C = x.shape
         m1, m2 = w1.shape[2], w1.shape[3]
         ctx.chain = ch = _chain(B, (s1, s2), (m1, m2), C, x.device, _lib.is_test_backend())
         st = _lib.current_stream(x.device)
         f32 = dict(dtype=torch.float32, device=x.device)
-        wp, wpt = torch.empty(ch.planes_floats, **f32), torch.empty(ch.planes_floats, **f32)
-        _capi.check(lib.ffno_fw2d_pack2(_p(w1), _p(w2), _p(wp), _p(wpt), C, m1, m2, st), "fw2d_pack2")
+        wp, wpt = _pack_corner_weights(ch, w1, w2, st)
         mid, cw = _scratch(ch)
         sx, out = torch.empty(ch.spec, **f32), torch.empty(m2, 2 * m1, B, 2, C, **f32)
         ch.analysis(x, mid, sx, cw, True, st)
@@ -663,10 +651,9 @@ class _GridToMixedModesFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.get_lib()
         sx, wpt = ctx.saved_tensors
         ch = ctx.chain
-        (s1, s2), (m1, m2), B, C = ch.Sp, ch.Ks, ch.B, ch.C
+        (s1, s2), B, C = ch.Sp, ch.B, ch.C
         st = _lib.current_stream(g.device)
         f32 = dict(dtype=torch.float32, device=g.device)
         dy = (g * float(np.sqrt(s1 * s2))).contiguous()
@@ -677,11 +664,7 @@ class _GridToMixedModesFn(torch.autograd.Function):
             dx = torch.empty(B, s1, s2, C, **f32)
             ch.mix(dy, wpt, dsx, False, st)
             ch.synthesis(dsx, mid, dx, cw, False, st)
-        part = torch.empty(ch.planes_floats, **f32)
-        gw1, gw2 = torch.empty(C, C, m1, m2, 2, **f32), torch.empty(C, C, m1, m2, 2, **f32)
-        ch.fw_grad_partial(sx, dy, part, st)
-        _capi.check(lib.ffno_fw2d_grad_reduce2(_p(part), _p(gw1), _p(gw2), C, m1, m2, 1, 0, st), "fw2d_grad_reduce2")
-        return dx, gw1, gw2
+        return (dx, *_corner_weight_grads(ch, sx, dy, st))
 
 
 def modes_to_grid(z, s1: int, s2: int):
@@ -697,9 +680,7 @@ def corners_to_grid(spec, s1: int, s2: int):
     """The x_out = None branch of the point-cloud SpectralConv2d (reference point_cloud_2d.py:70-74): complex64 corners
     [B, C, 2 modes1, modes2] in point_fft2d's layout are placed in rows [0, m1) and [s1 - m1, s1), columns [0, m2) of an
     s1 x (s2 // 2 + 1) spectrum and transformed by ``torch.fft.irfft2(., s=(s1, s2))`` -> channels-last real [B, s1, s2, C]."""
-    if not isinstance(spec, torch.Tensor) or spec.dtype != torch.complex64 or spec.dim() != 4:
-        raise TypeError("spec: expected a complex64 tensor [B, C, 2 m1, m2]")
-    return modes_to_grid(_modes_major(torch.view_as_real(spec)), s1, s2)
+    return modes_to_grid(_modes_major(_complex64(spec, 4, "spec [B, C, 2 m1, m2]", rank_error=TypeError)), s1, s2)
 
 
 def grid_to_mixed_modes(x, w1, w2):
@@ -727,14 +708,10 @@ class _MixCornerModesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, w1, w2, grid):
-        lib = _lib.get_lib()
         m2, R, B, _, C = z.shape
-        m1 = R // 2
-        ctx.chain = ch = _chain(B, grid, (m1, m2), C, z.device, _lib.is_test_backend())
+        ctx.chain = ch = _chain(B, grid, (R // 2, m2), C, z.device, _lib.is_test_backend())
         st = _lib.current_stream(z.device)
-        f32 = dict(dtype=torch.float32, device=z.device)
-        wp, wpt = torch.empty(ch.planes_floats, **f32), torch.empty(ch.planes_floats, **f32)
-        _capi.check(lib.ffno_fw2d_pack2(_p(w1), _p(w2), _p(wp), _p(wpt), C, m1, m2, st), "fw2d_pack2")
+        wp, wpt = _pack_corner_weights(ch, w1, w2, st)
         out = torch.empty_like(z)
         ch.mix(z, wp, out, True, st)
         ctx.save_for_backward(z, wpt)
@@ -742,22 +719,15 @@ class _MixCornerModesFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.get_lib()
         z, wpt = ctx.saved_tensors
         ch = ctx.chain
-        (m1, m2), C = ch.Ks, ch.C
         st = _lib.current_stream(g.device)
-        f32 = dict(dtype=torch.float32, device=g.device)
         g = g.contiguous()
         dz = None
         if ctx.needs_input_grad[0]:
             dz = torch.empty_like(z)
             ch.mix(g, wpt, dz, False, st)
-        part = torch.empty(ch.planes_floats, **f32)
-        gw1, gw2 = torch.empty(C, C, m1, m2, 2, **f32), torch.empty(C, C, m1, m2, 2, **f32)
-        ch.fw_grad_partial(z, g, part, st)
-        _capi.check(lib.ffno_fw2d_grad_reduce2(_p(part), _p(gw1), _p(gw2), C, m1, m2, 1, 0, st), "fw2d_grad_reduce2")
-        return dz, gw1, gw2, None
+        return (dz, *_corner_weight_grads(ch, z, g, st), None)
 
 
 def mix_corner_modes(z, w1, w2, grid=None):
@@ -782,11 +752,20 @@ _GRID_TABLES = {}
 
 
 def _grid_tables(s1, s2, device):
-    """tx[s1], ty[s2]: the reference's grid coordinates, float32(np.linspace(0, 1, s)) (point_cloud_2d.py:245-253)."""
-    key = (s1, s2, str(device))
+    """tx[s1], ty[s2]: the reference's grid coordinates, float32(np.linspace(0, 1, s)) (point_cloud_2d.py:245-253), and the pixel
+    coordinates [s1 * s2, 2] made of them, row-major.  One entry per (s1, s2, device), read only."""
+    key = (int(s1), int(s2), str(torch.device(device)))
     if key not in _GRID_TABLES:
-        _GRID_TABLES[key] = tuple(torch.tensor(np.linspace(0, 1, s), dtype=torch.float).to(device) for s in (s1, s2))
+        with torch.inference_mode(False):      # (kept across calls and saved for backward: never inference tensors)
+            tx, ty = (torch.tensor(np.linspace(0, 1, s), dtype=torch.float).to(device) for s in key[:2])
+            _GRID_TABLES[key] = (tx, ty, torch.cartesian_prod(tx, ty))
     return _GRID_TABLES[key]
+
+
+def latent_grid(s1: int, s2: int, device):
+    """The coordinates of the pixels of an s1 x s2 latent grid, row-major [s1 * s2, 2]: the reference's ``get_grid``
+    (point_cloud_2d.py:272-280) flattened, from the tables above."""
+    return _grid_tables(s1, s2, device)[2]
 
 
 class _GeoFNOPointwiseFn(torch.autograd.Function):
@@ -797,7 +776,7 @@ class _GeoFNOPointwiseFn(torch.autograd.Function):
         lib = _lib.get_lib()
         B, s1, s2, C = add.shape
         st = _lib.current_stream(add.device)
-        tx, ty = _grid_tables(s1, s2, add.device)
+        tx, ty, _ = _grid_tables(s1, s2, add.device)
         b = b1 if b2 is None else b1 + b2
         out, pre = torch.empty_like(add), torch.empty_like(add)
         _capi.check(lib.ffno_plin_pos_fwd(_p(x), C, _p(W), _p(b), _p(add), _p(gw), _p(tx), _p(ty), _p(out), C, _p(pre), B, s1, s2, C,
@@ -812,7 +791,7 @@ class _GeoFNOPointwiseFn(torch.autograd.Function):
         B, s1, s2, C = pre.shape
         P = B * s1 * s2
         st = _lib.current_stream(g.device)
-        tx, ty = _grid_tables(s1, s2, g.device)
+        tx, ty, _ = _grid_tables(s1, s2, g.device)
         g = g.contiguous()
         f32 = dict(dtype=torch.float32, device=g.device)
         dpre, dx, dW = torch.empty_like(pre), None, None

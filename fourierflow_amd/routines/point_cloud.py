@@ -70,7 +70,7 @@ class _TrainedParameters:
 
     def __init__(self, routine):
         seen, named = set(), []
-        skip = tuple("model." + pre for pre in getattr(routine.model, "unused_parameter_prefixes", ())) + ("iphi.fc_no_code.",)
+        skip = tuple("model." + pre for pre in routine.model.unused_parameter_prefixes) + ("iphi.fc_no_code.",)
         for n, p in routine.named_parameters():      # (shared tensors are reported once)
             if n.startswith(skip) or id(p) in seen:
                 continue
