@@ -2,22 +2,29 @@
 
 hipcc cross-compiles for gfx950 without a GPU, so this runs in the build container; the resulting
 .so is git-ignored but travels to the GPU box with the working tree.
+
+build_library() is the procedure itself -- stamps, lock, side-by-side compilation, link and rename -- and knows nothing about
+hipcc: the CPU wave-emulator flavour of the same sources (tests/emu/build_emu.py) goes through it with its own compiler and flags.
 """
 from __future__ import annotations
 
+import fcntl
+import glob
 import hashlib
 import os
 import shutil
-import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
+from subprocess import check_call
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(ROOT, "include")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libffno_hip.so")
-SOURCES = ["spectral.hip", "spectral_x3.hip", "ff.hip", "ffx.hip", "pointwise.hip", "velocity.hip", "spectral2d.hip", "plin.hip", "layer.hip", "layernorm.hip", "glin.hip", "infer.hip"]
 ARCH = "gfx950"
+FLAGS = (f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wno-unused-result")
 
 
 def _hipcc() -> str:
@@ -28,34 +35,100 @@ def _hipcc() -> str:
 
 
 def source_files():
-    return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    """Every translation unit of the library: csrc/*.hip, sorted.  (Experiments and micro-benchmarks keep their .hip files
+    under tools/.)"""
+    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    if not srcs:
+        raise FileNotFoundError(f"no *.hip sources in {CSRC}")
+    return srcs
 
 
-def _stamp() -> str:
-    h = hashlib.sha256()
-    headers = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")]
-    for p in sorted(source_files() + headers + [os.path.join(ROOT, "include", "ffno.h")]):
+def common_inputs():
+    """What every object depends on besides its own source: the headers of csrc/ and the ABI header."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "ffno.h")]
+
+
+def _stamp(paths, seed) -> str:
+    """The one hash of this build: `seed` (the flags, or the stamp of the common inputs) and the contents of `paths`."""
+    h = hashlib.sha256(repr(seed).encode())
+    for p in sorted(paths):
         with open(p, "rb") as f:
             h.update(f.read())
     return h.hexdigest()
 
 
+def _has_stamp(path, want) -> bool:
+    try:
+        with open(path + ".stamp") as f:
+            return os.path.exists(path) and f.read() == want
+    except OSError:
+        return False
+
+
+def build_library(lib, compiler, flags, link_flags=(), include_first=(), extra_inputs=(), force=False, verbose=False) -> str:
+    """source_files() -> `lib` with `compiler()` (looked up only when something has to be compiled); `include_first` directories
+    come before csrc/ and include/ on the include path and, being places, are no part of the stamps.  Compile + link under an
+    exclusive file lock (the ranks of a data-parallel job, or the workers of a parallel test run, may all find the library stale
+    at once: one builds, the others wait and find it fresh), into temporary names that are renamed into place: a concurrent
+    reader never sees a half-written .so.  Objects are rebuilt only when their own source, a common input or the flags changed
+    (per-object stamps), and the translation units compile side by side: a kernel edit costs one file's compile time."""
+    sources, outdir = source_files(), os.path.dirname(lib)
+    common = _stamp(common_inputs() + list(extra_inputs), tuple(flags))      # (headers are read once, not once per object)
+    stamp = _stamp(sources, common)
+    if not force and _has_stamp(lib, stamp):       # fresh: no lock, the workers of a parallel test run never queue for it
+        return lib
+    os.makedirs(outdir, exist_ok=True)
+    with open(os.path.join(outdir, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            # (checked again AFTER the lock was taken: another process may have finished the same build while we waited)
+            if not force and _has_stamp(lib, stamp):
+                return lib
+
+            def run(cmd):
+                if verbose:
+                    print("[ffno build]", " ".join(cmd), flush=True)
+                check_call(cmd)
+
+            includes = [x for d in (*include_first, CSRC, INCLUDE) for x in ("-I", d)]
+
+            def compile_one(src):
+                obj = os.path.join(outdir, os.path.basename(src) + ".o")
+                want = _stamp([src], common)
+                if force or not _has_stamp(obj, want):
+                    if os.path.exists(obj + ".stamp"):
+                        os.remove(obj + ".stamp")
+                    run([compiler(), *flags, *includes, "-c", src, "-o", obj])
+                    with open(obj + ".stamp", "w") as f:
+                        f.write(want)
+                return obj
+
+            with ThreadPoolExecutor(max_workers=min(len(sources), 16, os.cpu_count() or 4)) as ex:
+                objs = list(ex.map(compile_one, sources))
+            tag = f".tmp{os.getpid()}"
+            run([compiler(), *link_flags, "-shared", "-fPIC", "-o", lib + tag, *objs])
+            if os.path.exists(lib + ".stamp"):
+                os.remove(lib + ".stamp")          # never a new library beside an old stamp (or the reverse)
+            os.replace(lib + tag, lib)
+            with open(lib + ".stamp" + tag, "w") as f:
+                f.write(stamp)
+            os.replace(lib + ".stamp" + tag, lib + ".stamp")
+            return lib
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+
+
 def staleness() -> str:
-    """"fresh": the library on disk was built from exactly this tree's sources; "stale": from other sources (stamp mismatch / no
-    stamp / no library); "unverifiable": the sources or the ABI header are not readable here (an installed deployment that
-    ships the prebuilt .so without csrc/ or include/) -- nothing to compare the stamp with."""
-    stamp_file = LIB + ".stamp"
+    """"fresh": the library on disk was built from exactly this tree's sources with the default flags; "stale": from other
+    sources or flags (stamp mismatch / no stamp / no library); "unverifiable": the sources or the ABI header are not readable
+    here (an installed deployment that ships the prebuilt .so without csrc/ or include/) -- nothing to compare the stamp with."""
     if not os.path.exists(LIB):
         return "stale"
     try:
-        want = _stamp()
+        want = _stamp(source_files(), _stamp(common_inputs(), FLAGS))
     except OSError:
         return "unverifiable"
-    try:
-        with open(stamp_file) as f:
-            return "fresh" if f.read() == want else "stale"
-    except OSError:
-        return "stale"
+    return "fresh" if _has_stamp(LIB, want) else "stale"
 
 
 def is_stale() -> bool:
@@ -64,63 +137,8 @@ def is_stale() -> bool:
 
 
 def build(force: bool = False, verbose: bool = True, extra_flags=()) -> str:
-    """Compile + link under an exclusive file lock (the ranks of a data-parallel job may all find the library stale at once),
-    into temporary names that are renamed into place: a concurrent reader never sees a half-written .so."""
-    import fcntl
-    os.makedirs(LIBDIR, exist_ok=True)
-    stamp_file = LIB + ".stamp"
-    with open(os.path.join(LIBDIR, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            stamp = _stamp()
-            # (checked AFTER the lock was taken: another process may have finished the same build while we waited)
-            if not force and os.path.exists(LIB) and os.path.exists(stamp_file) and open(stamp_file).read() == stamp:
-                return LIB
-            tag = f".tmp{os.getpid()}"
-            # objects are rebuilt only when their own source, a header or the flags changed (per-object stamps), and the
-            # translation units compile side by side: a kernel edit costs one file's compile time, not eleven
-            from concurrent.futures import ThreadPoolExecutor
-            hdr = hashlib.sha256()
-            for p in sorted([os.path.join(CSRC, x) for x in os.listdir(CSRC) if x.endswith(".h")] + [os.path.join(ROOT, "include", "ffno.h")]):
-                with open(p, "rb") as f:
-                    hdr.update(f.read())
-            hdr.update(repr(tuple(extra_flags)).encode())
-
-            def compile_one(src):
-                obj = os.path.join(LIBDIR, os.path.basename(src) + ".o")
-                with open(src, "rb") as f:
-                    want = hashlib.sha256(hdr.digest() + f.read()).hexdigest()
-                try:
-                    if not force and os.path.exists(obj) and open(obj + ".stamp").read() == want:
-                        return obj
-                except OSError:
-                    pass
-                cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", src,
-                       "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-o", obj, "-Wno-unused-result", *extra_flags]
-                if verbose:
-                    print("[ffno build]", " ".join(cmd), flush=True)
-                if os.path.exists(obj + ".stamp"):
-                    os.remove(obj + ".stamp")
-                subprocess.check_call(cmd)
-                with open(obj + ".stamp", "w") as f:
-                    f.write(want)
-                return obj
-
-            with ThreadPoolExecutor(max_workers=max(1, min(len(source_files()), (os.cpu_count() or 4)))) as ex:
-                objs = list(ex.map(compile_one, source_files()))
-            cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB + tag, *objs]
-            if verbose:
-                print("[ffno build]", " ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-            if os.path.exists(stamp_file):
-                os.remove(stamp_file)          # never a new library beside an old stamp (or the reverse)
-            os.replace(LIB + tag, LIB)
-            with open(stamp_file + tag, "w") as f:
-                f.write(stamp)
-            os.replace(stamp_file + tag, stamp_file)
-            return LIB
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
+    """The gfx950 library; a build with `extra_flags` is stale to staleness(), which knows only the default ones."""
+    return build_library(LIB, _hipcc, FLAGS + tuple(extra_flags), link_flags=(f"--offload-arch={ARCH}",), force=force, verbose=verbose)
 
 
 if __name__ == "__main__":
