@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 13
+ABI_VERSION = 14
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -151,6 +151,13 @@ class GatherField(C.Structure):
     _fields_ = [("src", P), ("dst", P), ("src_sample", C.c_int64), ("src_offset", C.c_int64), ("src_q", C.c_int64),
                 ("src_r", C.c_int64), ("dst_sample", C.c_int64), ("dst_offset", C.c_int64), ("dst_q", C.c_int64),
                 ("dst_r", C.c_int64), ("Q", C.c_int32), ("R", C.c_int32)]
+
+
+class BgemmDesc(C.Structure):
+    """Mirror of ``ffno_bgemm_desc`` (include/ffno.h)."""
+    _fields_ = ([(n, P) for n in ("A", "B", "D", "bias", "gate", "resid")]
+                + [(f"{t}_{s}", C.c_int64) for t in "abd" for s in ("rs", "cs", "g0", "g1")]
+                + [(n, C.c_int32) for n in ("M", "N", "K", "G0", "G1")] + [("alpha", F), ("relu", C.c_int32), ("accumulate", C.c_int32)])
 
 
 GATHER_MAX_FIELDS = 8      # FFNO_GATHER_MAX_FIELDS
@@ -321,6 +328,15 @@ SIGNATURES = {
     "ffno_kf2d_derivs": (I, [P, P, F, I, I, P]),
     "ffno_kf2d_stage": (I, [P, P, P, F, F, F, F, F, F, F, I, F, F, F, F, I, I, I, P]),
     "ffno_kf2d_downsample": (I, [P, P, I, I, I, F, P]),
+    "ffno_bgemm_supported": (I, [P]),
+    "ffno_bgemm": (I, [P, P]),
+    "ffno_bgemm_splitk_slices": (I, [P]),
+    "ffno_bgemm_splitk_ws_floats": (SZ, [P]),
+    "ffno_bgemm_splitk": (I, [P, P, P]),
+    "ffno_bgemm_colsum_ws_floats": (SZ, [L, I]),
+    "ffno_bgemm_colsum": (I, [P, L, L, I, P, P, I, P]),
+    "ffno_bgemm_pack_fw": (I, [P, P, I, I, P]),
+    "ffno_bgemm_fold_fw": (I, [P, P, I, I, I, P]),
 }
 
 

@@ -1,0 +1,449 @@
+"""Host driver of the WIDE FNOFactorized2DBlock: widths 96 .. 256 (multiples of 32), where the tuned 32 / 64-channel kernels of
+engine.py do not apply (reference fourierflow/modules/factorized_fno/grid_2d.py:103-177, width-agnostic).
+
+The whole block, forward and backward, is composed from ONE kernel family, the batched strided fp32 GEMM of csrc/bgemm.hip
+(exact fp32 on v_mfma_f32_32x32x2_f32), channels-last [B, M, N, C] end to end:
+
+    lift, head          pointwise, M = pixels
+    DFT along y         F_y [2K x N] . x_line [N x C], batched over the B M lines           (forward and inverse, and their adjoints
+    DFT along x         F_x [2K x M] . x[b, :, n, :] [M x C], batched over (b, n)            through transposed strides)
+    mode mix            [lines x 2C] . [[Wr, Wi], [-Wi, Wr]] [2C x 2C], batched over k       (adjoint: transposed strides)
+    Fourier weight grad X[k]^T . dY[k], batched over k (split-K over the lines), then the fold (accumulated over layers, in a
+                        fixed order, with share_weight)
+    feed-forward        relu(s W1^T + b1) kept in HBM;  h W2^T + b2 + x through the residual epilogue;  backward: dh through
+                        the gate epilogue, ds, and dW1, dW2 (split-K), db1, db2 (column sum)
+    weight norm         the ffno_weightnorm_fwd / bwd descriptors of the main engine (they take any row length)
+
+The DFT tables are built once per (L, K) on the host in float64 and rounded to fp32: rows (re_k, im_k) interleaved, 1 / sqrt(L)
+and c_k (c_0 = 1, c_k = 2) folded in, the imaginary DC row of the inverse zeroed (irfft ignores imag(Y[0])).  K <= L // 2: the
+Nyquist bin is never kept.
+
+Every pass is recorded once per (input shape, save) as a list of C calls over pre-built descriptors and replayed.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import Dict, List, Tuple
+
+import numpy as np
+import torch
+
+from . import _capi, _lib
+from ._engine_core import EngineCore
+
+_p = _lib.ptr
+HEAD_DIM = 128
+WIDE_WIDTHS = tuple(range(96, 257, 32))
+MAX_HIDDEN = 1024
+MAX_MODES = 64
+
+
+def wide_supported(width: int) -> bool:
+    """The widths this engine is built for (the 32 / 64-channel kernel set of engine.py takes 32 and 64)."""
+    return width in WIDE_WIDTHS
+
+
+def dft_tables(L: int, K: int):
+    """(F [2K, L], Finv [L, 2K]) of rfft / irfft(norm='ortho') truncated to the K lowest bins, float64 -> fp32."""
+    n = np.arange(L, dtype=np.float64)
+    k = np.arange(K, dtype=np.float64)
+    th = 2.0 * np.pi * np.outer(k, n) / L
+    F = np.empty((2 * K, L))
+    F[0::2], F[1::2] = np.cos(th) / np.sqrt(L), -np.sin(th) / np.sqrt(L)
+    ck = np.where(k == 0, 1.0, 2.0)[:, None]
+    Fi = np.empty((2 * K, L))
+    Fi[0::2], Fi[1::2] = ck * np.cos(th) / np.sqrt(L), -ck * np.sin(th) / np.sqrt(L)
+    Fi[1] = 0.0          # C2R: imag(Y[0]) is ignored
+    return F.astype(np.float32), np.ascontiguousarray(Fi.T).astype(np.float32)
+
+
+class _Lin:
+    def __init__(self, prefix, rows, cols, wnorm):
+        self.prefix, self.rows, self.cols, self.wnorm = prefix, rows, cols, wnorm
+        self.weff = self.gweff = None
+
+
+class WideFFNO2DEngine(EngineCore):
+    can_return_view = True
+
+    def __init__(self, *, modes, width: int, input_dim: int, n_layers: int, factor: int, share_weight: bool,
+                 share_fork: bool = False, ff_weight_norm: bool = False, mode: str = "full", use_fork: bool = False,
+                 layer_norm: bool = False, n_ff_layers: int = 2, dropout: float = 0.0, in_dropout: float = 0.0,
+                 storage=None):
+        if not wide_supported(width):
+            raise ValueError(f"width={width} is outside the wide engine's set {WIDE_WIDTHS}")
+        C, H = width, factor * width
+        narrow = "widths 32 / 64 support it"
+
+        def refuse(option):
+            raise NotImplementedError(f"{option} is not built for width {width} (the wide GEMM engine); {narrow}")
+        if H > MAX_HIDDEN or factor < 1:
+            raise NotImplementedError(f"factor * width = {H} > {MAX_HIDDEN} is not built for the wide GEMM engine")
+        if use_fork:
+            refuse("use_fork=True")
+        if share_fork:
+            refuse("share_fork=True")
+        if layer_norm:
+            refuse("layer_norm=True")
+        if dropout or in_dropout:
+            refuse("dropout / in_dropout > 0")
+        if mode != "full":
+            refuse(f"mode={mode!r}")
+        if n_ff_layers != 2:
+            refuse(f"n_ff_layers={n_ff_layers}")
+        storage = os.environ.get("FFNO_STORAGE", "fp32") if storage is None else storage      # 
+        if storage != "fp32":
+            refuse(f"storage={storage!r}")
+        if not (0 < input_dim):
+            raise ValueError("input_dim must be positive")
+        self.Ks: Tuple[int, int] = tuple(modes) if isinstance(modes, (tuple, list)) else (int(modes),) * 2     # (K_y, K_x)
+        if len(self.Ks) != 2 or not all(1 <= k <= MAX_MODES for k in self.Ks):
+            raise ValueError(f"modes must be 1 .. {MAX_MODES} per axis, got {modes}")
+        self.C, self.H, self.Cin, self.L = C, H, input_dim, n_layers
+        self.share_weight, self.wnorm = bool(share_weight), bool(ff_weight_norm)
+
+        # parameter inventory: the registration order of FFNOEngine (engine.py), reference named_parameters() names
+        self.linears: Dict[str, _Lin] = {}
+        shapes: Dict[str, Tuple[int, ...]] = {}
+
+        def add_linear(prefix, rows, cols):
+            self.linears[prefix] = _Lin(prefix, rows, cols, self.wnorm)
+            if self.wnorm:
+                shapes[prefix + "weight_g"] = (rows, 1)
+                shapes[prefix + "weight_v"] = (rows, cols)
+            else:
+                shapes[prefix + "weight"] = (rows, cols)
+            shapes[prefix + "bias"] = (rows,)
+
+        add_linear("in_proj.", C, input_dim)
+        self.ff_prefix: List[str] = []
+        self.fw_names: List[Tuple[str, str]] = []
+        for l in range(n_layers):
+            fp = f"spectral_layers.{l}.backcast_ff."
+            self.ff_prefix.append(fp)
+            add_linear(fp + "layers.0.0.", H, C)
+            add_linear(fp + "layers.1.0.", C, H)
+            base = "fourier_weight." if share_weight else f"spectral_layers.{l}.fourier_weight."
+            names = (base + "0", base + "1")
+            self.fw_names.append(names)
+            for w, n in enumerate(names):
+                shapes.setdefault(n, (C, C, self.Ks[w], 2))
+        add_linear("out.0.", HEAD_DIM, C)
+        add_linear("out.1.", 1, HEAD_DIM)
+        self._lay_out(shapes)
+        self._fw_sets: List[Tuple[str, str]] = list(dict.fromkeys(self.fw_names))
+        self._fw_set_of = [self._fw_sets.index(n) for n in self.fw_names]
+
+        self.params: Dict[str, torch.Tensor] = {}
+        self.device = None
+        self.timer = None
+        self._issue_stream = 0
+        self._ws = {}
+        self._bind_sig = None
+        self._derived_sig = None
+        self._dirty = True
+        self._saved = None
+        self._tables = {}
+        self.dx = None
+
+    # ------------------------------------------------------------------------------------------------
+    def bind(self, params: Dict[str, torch.Tensor]):
+        """Attach the parameter tensors (unique reference names -> fp32 contiguous device tensors)."""
+        sig = tuple(params[n].data_ptr() for n in self.param_names) if all(n in params for n in self.param_names) else None
+        if sig is not None and self.params and sig == self._bind_sig:
+            self.params = {n: params[n] for n in self.param_names}
+            return
+        dev = self._validate(params)
+        self.params = {n: params[n] for n in self.param_names}
+        self._bind_sig = sig
+        self._dirty = True
+        self._ws = {}                 # the recorded passes hold parameter addresses
+        if dev != self.device:
+            self.device = dev
+            self._tables = {}
+        f32 = dict(dtype=torch.float32, device=dev)
+        C = self.C
+        self.gflat = torch.zeros(self.n_params, **f32)
+        n_eff = sum(l.rows * l.cols for l in self.linears.values()) if self.wnorm else 0
+        self.weff_flat = torch.empty(max(n_eff, 1), **f32)
+        self.gweff_flat = torch.zeros(max(n_eff, 1), **f32)
+        # packed per-mode block matrices of every Fourier weight set: packs[set][axis] [K][2C][2C]
+        self.packs = [[torch.empty(K, 2 * C, 2 * C, **f32) for K in self.Ks] for _ in self._fw_sets]
+        off, descs = 0, []
+        for lin in self.linears.values():
+            n = lin.rows * lin.cols
+            if lin.wnorm:
+                lin.weff = self.weff_flat[off:off + n].view(lin.rows, lin.cols)
+                lin.gweff = self.gweff_flat[off:off + n].view(lin.rows, lin.cols)
+                off += n
+                g, v = self.params[lin.prefix + "weight_g"], self.params[lin.prefix + "weight_v"]
+                descs.append(_capi.WnDesc(g.data_ptr(), v.data_ptr(), lin.weff.data_ptr(), lin.gweff.data_ptr(),
+                                          self.grad_view(lin.prefix + "weight_g").data_ptr(),
+                                          self.grad_view(lin.prefix + "weight_v").data_ptr(), lin.rows, lin.cols))
+            else:
+                lin.weff = self.params[lin.prefix + "weight"]
+                lin.gweff = self.grad_view(lin.prefix + "weight")
+        self._n_desc = len(descs)
+        self._max_rows = max(l.rows for l in self.linears.values())
+        self._desc_dev = _lib.device_table(_capi.WnDesc, descs, dev) if descs else None
+
+    def weights_changed(self):
+        """Parameter memory was written behind PyTorch's back (the optimiser kernel): the derived operands are stale."""
+        self._dirty = True
+
+    def _prepare_weights(self, st):
+        """Weight-norm products and packed Fourier blocks, rebuilt when a parameter was written."""
+        try:
+            sig = tuple(self.params[n]._version for n in self.param_names)
+        except RuntimeError:      # inference tensors carry no version counter: rebuild every pass
+            sig = None
+        if not self._dirty and sig is not None and sig == self._derived_sig:
+            return
+        lib = _lib.get_lib()
+        if self._desc_dev is not None:
+            self._k("weightnorm_fwd", lib.ffno_weightnorm_fwd, _p(self._desc_dev), self._n_desc, self._max_rows, st)
+        for names, packs in zip(self._fw_sets, self.packs):
+            for w in range(2):
+                self._k("wide_pack_fw", lib.ffno_bgemm_pack_fw, _p(self.params[names[w]]), _p(packs[w]), self.C, self.Ks[w], st)
+        self._derived_sig, self._dirty = sig, False
+
+    def _table(self, L: int, K: int):
+        t = self._tables.get((L, K))
+        if t is None:
+            F, Fi = dft_tables(L, K)
+            t = self._tables[(L, K)] = (torch.from_numpy(F).to(self.device), torch.from_numpy(Fi).to(self.device))
+        return t
+
+    # ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _gemm(ops, name, A, B, D, M, N, K, a, b, d, G0=1, G1=1, bias=None, gate=None, resid=None, relu=0, acc=0, split=False):
+        """Record D = epilogue(A . B); a / b / d = (row, column[, batch 0, batch 1]) strides in floats."""
+        ds = _capi.BgemmDesc()
+        ds.A, ds.B, ds.D = A.data_ptr(), B.data_ptr(), D.data_ptr()
+        ds.bias = None if bias is None else bias.data_ptr()
+        ds.gate = None if gate is None else gate.data_ptr()
+        ds.resid = None if resid is None else resid.data_ptr()
+        for t, s in (("a", a), ("b", b), ("d", d)):
+            s = tuple(s) + (0,) * (4 - len(s))
+            for f, v in zip(("rs", "cs", "g0", "g1"), s):
+                setattr(ds, f"{t}_{f}", int(v))
+        ds.M, ds.N, ds.K, ds.G0, ds.G1 = int(M), int(N), int(K), int(G0), int(G1)
+        ds.alpha, ds.relu, ds.accumulate = 1.0, int(relu), int(acc)
+        ops.append(("gemm_split" if split else "gemm", name, ds, (A, B, D, bias, gate, resid)))
+
+    def _colsum(self, ops, ws, name, X, P, N, out):
+        lib = _lib.get_lib()
+        ops.append(("call", name, lib.ffno_bgemm_colsum, (_p(X), N, P, N, _p(ws.cpart), _p(out), 0), (X, out)))
+
+    def _finish(self, ws, ops):
+        """Recorded ops -> (name, function, arguments) with the shared split-K partial buffer sized for the largest user."""
+        lib = _lib.get_lib()
+        need = max([int(lib.ffno_bgemm_splitk_ws_floats(ctypes.byref(o[2]))) for o in ops if o[0] == "gemm_split"] + [1])
+        if ws.part is None or ws.part.numel() < need:      # (the earlier, smaller buffer stays with the pass recorded over it)
+            ws.part = torch.empty(need, dtype=torch.float32, device=self.device)
+            ws.parts.append(ws.part)
+        out = []
+        for o in ops:
+            if o[0] == "gemm":
+                if not lib.ffno_bgemm_supported(ctypes.byref(o[2])):
+                    raise ValueError(f"{o[1]}: the GEMM kernels do not take this shape")
+                out.append((o[1], lib.ffno_bgemm, (ctypes.byref(o[2]),), o[2:]))
+            elif o[0] == "gemm_split":
+                out.append((o[1], lib.ffno_bgemm_splitk, (ctypes.byref(o[2]), _p(ws.part)), o[2:]))
+            else:
+                out.append((o[1], o[2], o[3], o[4]))
+        return out
+
+    def _run(self, ops, st):
+        for name, fn, args, _keep in ops:
+            self._k(name, fn, *args, st)
+
+    # ------------------------------------------------------------------------------------------------
+    def _workspace(self, B, M, N, save):
+        key = (B, M, N, bool(save))
+        ws = self._ws.get(key)
+        if ws is not None:
+            return ws
+        Ky, Kx = self.Ks
+        if Ky > N // 2 or Kx > M // 2:
+            raise ValueError(f"modes={self.Ks} (last axis, first axis) need 1 <= K <= L // 2 on a {M} x {N} grid")
+        C, H, L, Cin = self.C, self.H, self.L, self.Cin
+        P = B * M * N
+        if P * max(H, 2 * C) >= 2 ** 38:
+            raise ValueError("batch too large for one launch")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        ws = type("WS", (), {})()
+        ws.P, ws.part, ws.parts, ws.shape, ws.saves = P, None, [], (B, M, N), bool(save)
+        nslot = L if save else 1
+        ws.x = torch.empty(P, Cin, **f32)
+        ws.X = [torch.empty(P, C, **f32) for _ in range(2)]                  # layer inputs, ping-pong
+        ws.S = [torch.empty(P, C, **f32) for _ in range(nslot)]              # spectral output = feed-forward input
+        ws.Hh = [torch.empty(P, H, **f32) for _ in range(nslot)]             # hidden activations (their sign = the ReLU gate)
+        ws.SPy = [torch.empty(B * M, 2 * Ky * C, **f32) for _ in range(nslot)]      # forward spectra [line][k][re / im][C]
+        ws.SPx = [torch.empty(B * N, 2 * Kx * C, **f32) for _ in range(nslot)]
+        ws.SM = torch.empty(max(B * M * 2 * Ky, B * N * 2 * Kx) * C, **f32)         # mixed spectrum / adjoint spectrum
+        ws.SD = torch.empty_like(ws.SM)
+        ws.Bout = torch.empty(P, C, **f32)                                   # backcast of the last layer (the head's input)
+        ws.T0 = torch.empty(P, HEAD_DIM, **f32)
+        ws.y = torch.empty(P, 1, **f32)
+        ws.cpart = torch.empty(int(_lib.get_lib().ffno_bgemm_colsum_ws_floats(P, max(H, HEAD_DIM, C))), **f32)
+        ws.slot = (lambda l: l) if save else (lambda l: 0)
+        ws.fwd = self._record_forward(ws, B, M, N)
+        ws.bwd = ws.bwd_dx = None
+        if save:
+            ws.gy = torch.empty(P, 1, **f32)
+            ws.DT0 = torch.empty(P, HEAD_DIM, **f32)
+            ws.G = [torch.empty(P, C, **f32) for _ in range(3)]
+            ws.DH = torch.empty(P, H, **f32)
+            ws.DS = torch.empty(P, C, **f32)
+            ws.GW = torch.empty(max(self.Ks) * 4 * C * C, **f32)            # block gradient of one Fourier weight
+            ws.dx = torch.empty(P, Cin, **f32)
+            ws.bwd, ws.bwd_dx = self._record_backward(ws, B, M, N)
+        self._ws[key] = ws
+        while len(self._ws) > 4:
+            self._ws.pop(next(iter(self._ws)))
+        return ws
+
+    def _axes(self, B, M, N):
+        """Per spectral axis: (weight index, K, L, lines, G0, G1, (row, g0, g1) strides of a line's [L x C] image in a [P, C]
+        tensor)."""
+        C = self.C
+        Ky, Kx = self.Ks
+        return [(0, Ky, N, B * M, B * M, 1, (C, N * C, 0)),                 # fourier_weight[0]: the LAST axis (grid_2d.py:65-68)
+                (1, Kx, M, B * N, N, B, (N * C, C, M * N * C))]              # fourier_weight[1]: the first axis (grid_2d.py:83-86)
+
+    def _record_forward(self, ws, B, M, N):
+        C, H, L, Cin, P = self.C, self.H, self.L, self.Cin, ws.P
+        lin = self.linears
+        bias = lambda pfx: self.params[pfx + "bias"]      # noqa: E731
+        ops = []
+        g = self._gemm
+        g(ops, "wide_lift", ws.x, lin["in_proj."].weff, ws.X[0], P, C, Cin, (Cin, 1), (1, Cin), (C, 1), bias=bias("in_proj."))
+        for l in range(L):
+            sl = ws.slot(l)
+            X, Xn, S, Hh = ws.X[l % 2], ws.X[(l + 1) % 2], ws.S[sl], ws.Hh[sl]
+            packs = self.packs[self._fw_set_of[l]]
+            for w, K, Ln, R, G0, G1, (rs, s0, s1) in self._axes(B, M, N):
+                F, Fi = self._table(Ln, K)
+                SP = (ws.SPy if w == 0 else ws.SPx)[sl]
+                kc = 2 * K * C
+                g(ops, f"wide_dft{w}", F, X, SP, 2 * K, C, Ln, (Ln, 1), (rs, 1, s0, s1), (C, 1, kc, G0 * kc), G0, G1)
+                g(ops, f"wide_mix{w}", SP, packs[w], ws.SM, R, 2 * C, 2 * C, (kc, 1, 2 * C), (2 * C, 1, 4 * C * C), (kc, 1, 2 * C), K)
+                g(ops, f"wide_idft{w}", Fi, ws.SM, S, Ln, C, 2 * K, (2 * K, 1), (C, 1, kc, G0 * kc), (rs, 1, s0, s1), G0, G1, acc=w)
+            pfx = self.ff_prefix[l]
+            l0, l1 = pfx + "layers.0.0.", pfx + "layers.1.0."
+            g(ops, "wide_ff1", S, lin[l0].weff, Hh, P, H, C, (C, 1), (1, C), (H, 1), bias=bias(l0), relu=1)
+            if l < L - 1:
+                g(ops, "wide_ff2", Hh, lin[l1].weff, Xn, P, C, H, (H, 1), (1, H), (C, 1), bias=bias(l1), resid=X)
+            else:     # the head reads the last BACKCAST, not x + b (grid_2d.py:175)
+                g(ops, "wide_ff2", Hh, lin[l1].weff, ws.Bout, P, C, H, (H, 1), (1, H), (C, 1), bias=bias(l1))
+        g(ops, "wide_head0", ws.Bout, lin["out.0."].weff, ws.T0, P, HEAD_DIM, C, (C, 1), (1, C), (HEAD_DIM, 1), bias=bias("out.0."))
+        g(ops, "wide_head1", ws.T0, lin["out.1."].weff, ws.y, P, 1, HEAD_DIM, (HEAD_DIM, 1), (1, HEAD_DIM), (1, 1), bias=bias("out.1."))
+        return self._finish(ws, ops)
+
+    def _record_backward(self, ws, B, M, N):
+        lib = _lib.get_lib()
+        C, H, L, Cin, P = self.C, self.H, self.L, self.Cin, ws.P
+        lin = self.linears
+        gb = lambda pfx: self.grad_view(pfx + "bias")      # noqa: E731
+        ops = []
+        g, cs = self._gemm, self._colsum
+        o0, o1 = lin["out.0."], lin["out.1."]
+        # head: y = T0 W1^T + b1,  T0 = Bout W0^T + b0
+        g(ops, "wide_head1_dw", ws.gy, ws.T0, o1.gweff, 1, HEAD_DIM, P, (1, 1), (HEAD_DIM, 1), (HEAD_DIM, 1), split=True)
+        cs(ops, ws, "wide_head1_db", ws.gy, P, 1, gb("out.1."))
+        g(ops, "wide_head1_bwd", ws.gy, o1.weff, ws.DT0, P, HEAD_DIM, 1, (1, 1), (HEAD_DIM, 1), (HEAD_DIM, 1))
+        g(ops, "wide_head0_dw", ws.DT0, ws.Bout, o0.gweff, HEAD_DIM, C, P, (1, HEAD_DIM), (C, 1), (C, 1), split=True)
+        cs(ops, ws, "wide_head0_db", ws.DT0, P, HEAD_DIM, gb("out.0."))
+        g(ops, "wide_head0_bwd", ws.DT0, o0.weff, ws.G[0], P, C, HEAD_DIM, (HEAD_DIM, 1), (C, 1), (C, 1))
+        cur, gx = 0, None                # ws.G[cur]: dL/d(backcast of layer l);  gx: dL/dx_{l+1} (None above the last layer)
+        seen = set()
+        for l in range(L - 1, -1, -1):
+            sl = ws.slot(l)
+            S, Hh, Gb = ws.S[sl], ws.Hh[sl], ws.G[cur]
+            pfx = self.ff_prefix[l]
+            l0, l1 = pfx + "layers.0.0.", pfx + "layers.1.0."
+            g(ops, "wide_ff2_dw", Gb, Hh, lin[l1].gweff, C, H, P, (1, C), (H, 1), (H, 1), split=True)
+            cs(ops, ws, "wide_ff2_db", Gb, P, C, gb(l1))
+            g(ops, "wide_ff2_bwd", Gb, lin[l1].weff, ws.DH, P, H, C, (C, 1), (H, 1), (H, 1), gate=Hh)
+            g(ops, "wide_ff1_dw", ws.DH, S, lin[l0].gweff, H, C, P, (1, H), (C, 1), (C, 1), split=True)
+            cs(ops, ws, "wide_ff1_db", ws.DH, P, H, gb(l0))
+            g(ops, "wide_ff1_bwd", ws.DH, lin[l0].weff, ws.DS, P, C, H, (H, 1), (C, 1), (C, 1))
+            # dL/dx_l = (dL/dx_{l+1}, the residual) + the adjoints of the two spectral branches
+            nxt = [i for i in range(3) if i != cur and (gx is None or ws.G[i] is not gx)][0]
+            Gn = ws.G[nxt]
+            packs = self.packs[self._fw_set_of[l]]
+            names = self.fw_names[l]
+            for w, K, Ln, R, G0, G1, (rs, s0, s1) in self._axes(B, M, N):
+                F, Fi = self._table(Ln, K)
+                SP = (ws.SPy if w == 0 else ws.SPx)[sl]
+                kc = 2 * K * C
+                g(ops, f"wide_idft{w}_adj", Fi, ws.DS, ws.SD, 2 * K, C, Ln, (1, 2 * K), (rs, 1, s0, s1), (C, 1, kc, G0 * kc), G0, G1)
+                g(ops, f"wide_fw{w}_grad", SP, ws.SD, ws.GW, 2 * C, 2 * C, R, (1, kc, 2 * C), (kc, 1, 2 * C), (2 * C, 1, 4 * C * C), K,
+                  split=True)
+                ops.append(("call", f"wide_fw{w}_fold", lib.ffno_bgemm_fold_fw,
+                            (_p(ws.GW), _p(self.grad_view(names[w])), C, K, int(names[w] in seen)), ()))
+                seen.add(names[w])
+                g(ops, f"wide_mix{w}_adj", ws.SD, packs[w], ws.SM, R, 2 * C, 2 * C, (kc, 1, 2 * C), (1, 2 * C, 4 * C * C), (kc, 1, 2 * C), K)
+                g(ops, f"wide_dft{w}_adj", F, ws.SM, Gn, Ln, C, 2 * K, (1, Ln), (C, 1, kc, G0 * kc), (rs, 1, s0, s1), G0, G1,
+                  resid=gx if w == 0 else None, acc=w)
+            gx, cur = Gn, nxt             # the block's residual x_{l+1} = x_l + b_l: both gradients are dL/dx_l from here on
+        gl = ws.G[cur]
+        g(ops, "wide_lift_dw", gl, ws.x, lin["in_proj."].gweff, C, Cin, P, (1, C), (Cin, 1), (Cin, 1), split=True)
+        cs(ops, ws, "wide_lift_db", gl, P, C, gb("in_proj."))
+        if self._desc_dev is not None:
+            ops.append(("call", "weightnorm_bwd", lib.ffno_weightnorm_bwd, (_p(self._desc_dev), self._n_desc, self._max_rows), ()))
+        dx_ops = []
+        g(dx_ops, "wide_lift_bwd", gl, lin["in_proj."].weff, ws.dx, P, Cin, C, (C, 1), (Cin, 1), (Cin, 1))
+        return self._finish(ws, ops), self._finish(ws, dx_ops)
+
+    # ------------------------------------------------------------------------------------------------
+    def forward(self, x: torch.Tensor, save_for_backward: bool, training=None, own_output: bool = True) -> torch.Tensor:
+        """x [B, M, N, input_dim] -> forecast [B, M, N, 1]; ``own_output=False`` returns a view of the engine's buffer."""
+        _lib.require_device_tensor(x, "x")
+        if x.dim() != 4 or x.shape[-1] != self.Cin:
+            raise ValueError(f"expected x of shape [B, M, N, {self.Cin}], got {tuple(x.shape)}")
+        if not self.params:
+            raise RuntimeError("bind() the parameters first")
+        B, M, N = (int(v) for v in x.shape[:3])
+        ws = self._workspace(B, M, N, save_for_backward)
+        st = _lib.current_stream(self.device)
+        self._issue_stream = st
+        self._prepare_weights(st)
+        ws.x.copy_(x.reshape(ws.P, self.Cin))
+        self._run(ws.fwd, st)
+        self._saved = ws if save_for_backward else None
+        self._last = ws
+        y = ws.y.view(B, M, N, 1)
+        return y.clone() if own_output else y
+
+    def backward(self, gy: torch.Tensor, need_dx: bool = False) -> torch.Tensor:
+        """gy = dL/dforecast [B, M, N, 1] -> the flat gradient buffer (``param_names`` order); ``self.dx`` with ``need_dx``."""
+        _lib.require_device_tensor(gy, "gy")
+        ws = self._saved
+        if ws is None:
+            raise RuntimeError("backward() needs a preceding forward(save_for_backward=True)")
+        self._saved = None
+        st = _lib.current_stream(self.device)
+        self._issue_stream = st
+        ws.gy.copy_(gy.reshape(ws.P, 1))
+        self._run(ws.bwd, st)
+        self.dx = None
+        if need_dx:
+            self._run(ws.bwd_dx, st)
+            self.dx = ws.dx.view(*ws.shape, self.Cin).clone()
+        return self.gflat
+
+    def relu_active_sets(self) -> Dict[Tuple[str, int], torch.Tensor]:
+        """{("backcast", layer): [pixels, hidden] bool}: the ReLU decisions of the last forward(save_for_backward=True) (tests:
+        the oracle is evaluated on the same linear piece)."""
+        ws = getattr(self, "_last", None)
+        if ws is None or not ws.saves:
+            raise RuntimeError("relu_active_sets() needs a preceding forward(save_for_backward=True)")
+        return {("backcast", l): ws.Hh[l] > 0 for l in range(self.L)}
+
+    def workspace_bytes_per_layer(self, B: int, M: int, N: int) -> int:
+        """What one more layer keeps for the backward pass: s, h and the two forward spectra."""
+        Ky, Kx = self.Ks
+        return 4 * (B * M * N * (self.C + self.H) + 2 * self.C * (B * M * Ky + B * N * Kx))

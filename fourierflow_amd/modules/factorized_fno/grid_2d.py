@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine import FFNO2DEngine
+from ...engine_wide import WideFFNO2DEngine, wide_supported
 from .._engine_module import EngineModule
 from ..feedforward import FeedForward
 from ..linear import WNLinear
@@ -89,13 +90,16 @@ class FNOFactorized2DBlock(EngineModule, nn.Module):
 
         self.out = nn.Sequential(WNLinear(width, 128, wnorm=ff_weight_norm), WNLinear(128, 1, wnorm=ff_weight_norm))
 
-    def engine(self) -> FFNO2DEngine:
+    def engine(self):
+        """The host engine: the tuned 32 / 64-channel kernels (FFNO2DEngine), or the GEMM-composed WideFFNO2DEngine for widths
+        96 .. 256; any other width raises FFNO2DEngine's ValueError."""
         if self._engine is None:
-            self._engine = FFNO2DEngine(modes=self.modes, width=self.width, input_dim=self.input_dim,
-                                        n_layers=self.n_layers, factor=self.factor, share_weight=self.share_weight,
-                                        share_fork=self.share_fork, ff_weight_norm=self.ff_weight_norm, mode=self.mode,
-                                        use_fork=self.use_fork, layer_norm=self.layer_norm, n_ff_layers=self.n_ff_layers,
-                                        dropout=self.dropout, in_dropout=self.in_dropout)
+            cls = WideFFNO2DEngine if wide_supported(self.width) else FFNO2DEngine
+            self._engine = cls(modes=self.modes, width=self.width, input_dim=self.input_dim,
+                               n_layers=self.n_layers, factor=self.factor, share_weight=self.share_weight,
+                               share_fork=self.share_fork, ff_weight_norm=self.ff_weight_norm, mode=self.mode,
+                               use_fork=self.use_fork, layer_norm=self.layer_norm, n_ff_layers=self.n_ff_layers,
+                               dropout=self.dropout, in_dropout=self.in_dropout)
         return self._engine
 
     def forward(self, x, **kwargs):

@@ -97,6 +97,9 @@ class Grid2DRolloutExperiment(EpochEndMixin, CheckpointMixin, nn.Module):
         """loss of the rollout, backward through every step, (all-reduce,) fused AdamW: one optimisation step."""
         tr = self.trainer()
         eng = tr.engine
+        if not hasattr(eng, "zero_grad"):
+            raise NotImplementedError(f"{type(eng).__name__} does not add up the gradients of the passes of a rollout "
+                                      "(back-propagation through time): not built for this operator / width")
         self.train()
         self.conv.fused_grad_accumulation = True      # parameter gradients of all n_steps passes add up inside the engine
         self.conv.max_live_passes = max(self.conv.max_live_passes, self.n_steps)

@@ -82,8 +82,8 @@ const char* ffno_build_target(void);
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
  * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
  * in the same way.  12: ffno_ns2d_cn_update_harmonic / ffno_ns2d_harmonic_force, likewise.  13: ffno_nudft_axis_* /
- * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise. */
-#define FFNO_ABI_VERSION 13
+ * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise.  14: ffno_bgemm*, likewise. */
+#define FFNO_ABI_VERSION 14
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -1328,6 +1328,58 @@ int ffno_kf2d_stage(float* w_h, float* h, const float* adv_h, float viscosity, f
                     float beta, float gamma, float mu, int kf, float f_re, float f_im, float k0, float adv_scale, int first, int B,
                     int N, void* stream);
 int ffno_kf2d_downsample(const float* vel2, float* out, int B, int N, int m, float length, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched strided fp32 GEMM: the kernel family of the WIDE F-FNO block (widths 96 .. 256, engine_wide.py), where the tuned
+ * 32 / 64-channel kernels do not apply.  The reference block is width-agnostic (grid_2d.py:103-152); its op sequence per layer,
+ * channels-last x [B][M][N][C], is served by this one call:
+ *     lift / head        in_proj, out.0, out.1 (grid_2d.py:157,175):    [pixels x Cin] . W^T + b
+ *     rfft(norm=ortho) along an axis, first K bins (grid_2d.py:60,76):  F [2K x L] . x_line [L x C], batched over the lines
+ *     einsum("bixy,ioy->boxy") per mode (grid_2d.py:65-68,83-86):       [lines x 2C] . [[Wr, Wi], [-Wi, Wr]] [2C x 2C], batched over k
+ *     irfft(n=L, norm=ortho) of the zero-padded spectrum (:72,90):      Finv [L x 2K] . s_line [2K x C]
+ *     FeedForward (feedforward.py:13-23):  relu(s W1^T + b1),  h W2^T + b2 + x (the block's residual, grid_2d.py:169)
+ *   and their adjoints (the same call with transposed strides), the weight gradients (split-K) and bias gradients (column sum).
+ *
+ *     D[g1][g0][m][n] = epilogue( alpha * sum_k A[g1][g0][m][k] B[g1][g0][k][n] )
+ *     epilogue(v):  v += bias[n];  relu: v = max(v, 0);  gate: v = gate[m][n] > 0 ? v : 0;  v += resid[m][n];  accumulate: v += D
+ *   Element (m, k) of A is A[g1 a_g1 + g0 a_g0 + m a_rs + k a_cs] (floats), likewise B (k, n) and D (m, n); gate and resid are
+ *   addressed like D.  A batch stride of 0 shares an operand.  Any M, N, K, G0, G1 >= 1.  Exact fp32 (v_mfma_f32_32x32x2_f32:
+ *   a k-ordered fmaf chain per output element, whatever the tile variant), deterministic.
+ *   FFNO_EINVAL: NULL desc / A / B / D, a size < 1.  FFNO_EUNSUPPORTED: a zero row, column or (used) batch stride of D, more than
+ *   2^31 - 1 workgroups.  ffno_bgemm_supported: 1 iff ffno_bgemm would take the descriptor.
+ *   ffno_bgemm_splitk: the same product with K cut into ffno_bgemm_splitk_slices(desc) slices of at most 4096 rows (fewer rows
+ *   while the launch is small); the raw slice sums go to `partial` (ffno_bgemm_splitk_ws_floats(desc) floats) and a second launch
+ *   adds them in slice order and applies the epilogue.  No atomics: two calls give the same bits.
+ *   ffno_bgemm_colsum: out[n] (+)= sum_p X[p row_stride + n], p < P, n < N, in slices of 1024 rows through `partial`
+ *   (ffno_bgemm_colsum_ws_floats(P, N) floats), the same way.  P <= 65535 * 1024.
+ *   ffno_bgemm_pack_fw: fourier_weight w [C][C][K][2] (in, out, mode, re / im) -> Wb [K][2C][2C] = [[Wr, Wi], [-Wi, Wr]], so that
+ *   [xr | xi] . Wb[k] = [re | im] of x_k . w_k.   ffno_bgemm_fold_fw: a gradient G [K][2C][2C] = [[G11, G12], [G21, G22]] of the
+ *   blocks -> dw [C][C][K][2] (+)= (G11 + G22, G12 - G21);  accumulate = 1 serves share_weight.
+ * Workspaces are the caller's; every call only enqueues on `stream`.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct ffno_bgemm_desc {
+    const float* A;
+    const float* B;
+    float* D;
+    const float* bias;  /* [N] or NULL */
+    const float* gate;  /* or NULL */
+    const float* resid; /* or NULL */
+    int64_t a_rs, a_cs, a_g0, a_g1;
+    int64_t b_rs, b_cs, b_g0, b_g1;
+    int64_t d_rs, d_cs, d_g0, d_g1;
+    int32_t M, N, K, G0, G1;
+    float alpha;
+    int32_t relu, accumulate;
+} ffno_bgemm_desc;
+int ffno_bgemm_supported(const ffno_bgemm_desc* desc);
+int ffno_bgemm(const ffno_bgemm_desc* desc, void* stream);
+int ffno_bgemm_splitk_slices(const ffno_bgemm_desc* desc);
+size_t ffno_bgemm_splitk_ws_floats(const ffno_bgemm_desc* desc);
+int ffno_bgemm_splitk(const ffno_bgemm_desc* desc, float* partial, void* stream);
+size_t ffno_bgemm_colsum_ws_floats(long P, int N);
+int ffno_bgemm_colsum(const float* X, long row_stride, long P, int N, float* partial, float* out, int accumulate, void* stream);
+int ffno_bgemm_pack_fw(const float* w, float* Wb, int C, int K, void* stream);
+int ffno_bgemm_fold_fw(const float* G, float* dw, int C, int K, int accumulate, void* stream);
 
 /* small utilities used by the host driver */
 int ffno_axpy(float* y, const float* x, float alpha, size_t n, void* stream); /* y += alpha*x */
