@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 14
+ABI_VERSION = 15
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -337,6 +337,9 @@ SIGNATURES = {
     "ffno_bgemm_colsum": (I, [P, L, L, I, P, P, I, P]),
     "ffno_bgemm_pack_fw": (I, [P, P, I, I, P]),
     "ffno_bgemm_fold_fw": (I, [P, P, I, I, I, P]),
+    "ffno_pad_supported": (I, [I, P, P, I]),
+    "ffno_pad_embed": (I, [P, P, L, I, P, P, I, P]),
+    "ffno_pad_crop": (I, [P, P, L, I, P, P, I, P]),
 }
 
 

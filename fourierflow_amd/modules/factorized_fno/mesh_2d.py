@@ -5,7 +5,8 @@ Same classes, constructor signatures, parameter names/shapes and forward contrac
 (``forward(x[B,X,Y,input_dim-2]) -> [B,X,Y,1]``).  Differences from the torus block that matter here: ``modes_x`` and
 ``modes_y`` are independent, ``fourier_weight[0]`` mixes the FIRST spatial axis (mesh_2d.py:92-96) and ``[1]`` the last
 (mesh_2d.py:71-75), the lifted features are zero-padded by 8 on both axes and the last backcast is cropped before the
-head (mesh_2d.py:150,158).  Pad and crop are index maps inside the lift / head kernels.  HIP only: CPU tensors raise.
+head (mesh_2d.py:150,158).  Pad and crop are index maps inside the lift / head kernels at widths 32 / 64, two copy kernels
+around the dense lift / head GEMMs at widths 96 .. 256 (engine_wide.py).  HIP only: CPU tensors raise.
 """
 import numpy as np
 import torch
@@ -13,6 +14,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine import FFNOEngine
+from ...engine_wide import WideFFNOMeshEngine, wide_supported
 from .._engine_module import EngineModule
 from ..feedforward import FeedForward
 from ..linear import WNLinear
@@ -68,12 +70,16 @@ class FNOFactorizedMesh2D(EngineModule, nn.Module):
         self.layer_norm = bool(layer_norm)
         self.n_ff_layers = n_ff_layers
 
-    def engine(self) -> FFNOEngine:
+    def engine(self):
+        """The host engine: the tuned 32 / 64-channel kernels (FFNOEngine), or the GEMM-composed WideFFNOMeshEngine for widths
+        96 .. 256; any other width raises FFNOEngine's ValueError.  ``self.padding`` is read here, at the first call."""
         if self._engine is None:
-            self._engine = FFNOEngine(modes=(self.modes_x, self.modes_y), width=self.width, input_dim=self.input_dim,
-                                      n_layers=self.n_layers, factor=self.factor, share_weight=self.share_weight,
-                                      share_fork=False, ff_weight_norm=self.ff_weight_norm, mode="full", spatial_dims=2,
-                                      padding=self.padding, output_dim=1, first_axis_first=True, layer_norm=self.layer_norm, n_ff_layers=self.n_ff_layers)
+            cls = WideFFNOMeshEngine if wide_supported(self.width) else FFNOEngine
+            self._engine = cls(modes=(self.modes_x, self.modes_y), width=self.width, input_dim=self.input_dim,
+                               n_layers=self.n_layers, factor=self.factor, share_weight=self.share_weight,
+                               share_fork=False, ff_weight_norm=self.ff_weight_norm, mode="full", spatial_dims=2,
+                               padding=self.padding, output_dim=1, first_axis_first=True, layer_norm=self.layer_norm,
+                               n_ff_layers=self.n_ff_layers)
         return self._engine
 
     def get_grid(self, shape, device):

@@ -4,7 +4,8 @@
 Same classes, constructor signatures, parameter names/shapes and forward contract
 (``forward(x[B,X,Y,Z,input_dim-3]) -> [B,X,Y,Z,output_dim]``).  The three per-axis branches run on the same
 HIP spectral kernels as the 2-D block through reshaped views; the +8 zero padding and the final crop are
-index maps inside the lift / head kernels (no pad or crop copies).  HIP only: CPU tensors raise.
+index maps inside the lift / head kernels (no pad or crop copies).  Widths 96 .. 256 run on the GEMM-composed wide mesh engine
+(engine_wide.py), which pads and crops with two copy kernels.  HIP only: CPU tensors raise.
 """
 import numpy as np
 import torch
@@ -12,6 +13,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ...engine import FFNOEngine
+from ...engine_wide import WideFFNOMeshEngine, wide_supported
 from .._engine_module import EngineModule
 from ..feedforward import FeedForward
 from ..linear import WNLinear
@@ -66,13 +68,17 @@ class FNOFactorizedMesh3D(EngineModule, nn.Module):
         self.layer_norm = bool(layer_norm)
         self.n_ff_layers = n_ff_layers
 
-    def engine(self) -> FFNOEngine:
+    def engine(self):
+        """The host engine: the tuned 32 / 64-channel kernels (FFNOEngine), or the GEMM-composed WideFFNOMeshEngine for widths
+        96 .. 256; any other width raises FFNOEngine's ValueError.  ``self.padding`` is read here, at the first call."""
         if self._engine is None:
-            self._engine = FFNOEngine(modes=(self.modes_x, self.modes_y, self.modes_z), width=self.width,
-                                      input_dim=self.input_dim, n_layers=self.n_layers, factor=self.factor,
-                                      share_weight=self.share_weight, share_fork=False,
-                                      ff_weight_norm=self.ff_weight_norm, mode="full", spatial_dims=3,
-                                      padding=self.padding, output_dim=self.output_dim, layer_norm=self.layer_norm, n_ff_layers=self.n_ff_layers)
+            cls = WideFFNOMeshEngine if wide_supported(self.width) else FFNOEngine
+            self._engine = cls(modes=(self.modes_x, self.modes_y, self.modes_z), width=self.width,
+                               input_dim=self.input_dim, n_layers=self.n_layers, factor=self.factor,
+                               share_weight=self.share_weight, share_fork=False,
+                               ff_weight_norm=self.ff_weight_norm, mode="full", spatial_dims=3,
+                               padding=self.padding, output_dim=self.output_dim, layer_norm=self.layer_norm,
+                               n_ff_layers=self.n_ff_layers)
         return self._engine
 
     def get_grid(self, shape, device):

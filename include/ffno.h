@@ -82,8 +82,8 @@ const char* ffno_build_target(void);
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
  * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
  * in the same way.  12: ffno_ns2d_cn_update_harmonic / ffno_ns2d_harmonic_force, likewise.  13: ffno_nudft_axis_* /
- * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise.  14: ffno_bgemm*, likewise. */
-#define FFNO_ABI_VERSION 14
+ * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise.  14: ffno_bgemm*, likewise.  15: ffno_pad_*, likewise. */
+#define FFNO_ABI_VERSION 15
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -1380,6 +1380,24 @@ size_t ffno_bgemm_colsum_ws_floats(long P, int N);
 int ffno_bgemm_colsum(const float* X, long row_stride, long P, int N, float* partial, float* out, int accumulate, void* stream);
 int ffno_bgemm_pack_fw(const float* w, float* Wb, int C, int K, void* stream);
 int ffno_bgemm_fold_fw(const float* G, float* dw, int C, int K, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Zero padding and cropping of channels-last fp32 activations: the WIDE mesh operators (FNOFactorizedMesh2D / Mesh3D at widths
+ * 96 .. 256, engine_wide.py) lift and apply the head on the data grid and run their layers on the padded one.
+ *   ffno_pad_embed: dense [B][s_0]..[s_{nd-1}][C] -> padded [B][s_0 + p_0]..[s_{nd-1} + p_{nd-1}][C].  Replaces
+ *       F.pad(x, [0, padding, 0, padding(, 0, padding)]) of the lifted features (mesh_2d.py:150, mesh_3d.py:165): the pad lies at the
+ *       END of every axis.  EVERY element of `padded` is written, the pad region with 0.0f, so a reused buffer may be the target.
+ *   ffno_pad_crop:  padded -> dense, its adjoint.  Replaces b[..., :-padding, :-padding(, :-padding), :] of the last backcast
+ *       (mesh_2d.py:158, mesh_3d.py:173).  In the backward pass the two swap roles.
+ *   sizes[nd] (the DENSE extents) and pads[nd] are HOST arrays, read before the call returns.  nd in 1 .. 3, sizes >= 1,
+ *   pads >= 0 (0 on every axis is a copy), C % 4 == 0, both tensors 16-byte aligned: the kernel moves float4 elements in a
+ *   grid-stride loop (at most 2048 blocks of 256 threads) with 64-bit offsets.  ffno_pad_supported: 1 iff the two take the shape.
+ *   FFNO_EINVAL: NULL or misaligned tensor, B < 1.  FFNO_EUNSUPPORTED: what ffno_pad_supported refuses, or 2^40 float4 or more.
+ * Exact (a copy); no workspace, no atomics; every call only enqueues on `stream`.
+ * --------------------------------------------------------------------------------------------- */
+int ffno_pad_supported(int nd, const int* sizes, const int* pads, int C);
+int ffno_pad_embed(const float* dense, float* padded, long B, int nd, const int* sizes, const int* pads, int C, void* stream);
+int ffno_pad_crop(const float* padded, float* dense, long B, int nd, const int* sizes, const int* pads, int C, void* stream);
 
 /* small utilities used by the host driver */
 int ffno_axpy(float* y, const float* x, float alpha, size_t n, void* stream); /* y += alpha*x */

@@ -10,6 +10,11 @@ Every side gets warm-up calls, then --rounds rounds in which the sides alternate
 at least --seconds of timed work over the rounds; host clock around calls that end in a device synchronise; the median of the
 rounds and their spread.  One JSON line; profiles/wide_engine.md holds a run.  From the repository root:  python tools/time_wide.py
 
+  --mesh airfoil|plasticity   the wide MESH operators instead (WideFFNOMeshEngine; the pad / crop kernels of csrc/meshpad.hip):
+                         airfoil     FNOFactorizedMesh2D, 221 x 51 (padded 229 x 59), batch 10, modes 32 / 16, 4 layers
+                         plasticity  FNOFactorizedMesh3D, 101 x 31 x 20 (padded 109 x 39 x 28), batch 2, modes 32 / 12 / 8, 4 layers
+                         at the reference configs' other hyper-parameters, against oracle.ffno_oracle.ffno_mesh2d / ffno_mesh3d;
+                         no width-64 row.  profiles/wide_mesh.md holds a run.  Goes with --sites and --only as well.
   --sites --width W      per call site of one wide training step: launches, shape-derived FLOPs, device time (HIP events
                          around every launch) and the achieved TF/s against the 157 TF fp32 matrix peak
   --only fwd|step --width W [--iters I]   that side alone after a warm-up: what a `rocprofv3 --kernel-trace --stats` run of its
@@ -33,6 +38,7 @@ ap.add_argument("--grid", type=int, default=64)
 ap.add_argument("--factor", type=int, default=4)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--seconds", type=float, default=1.0)
+ap.add_argument("--mesh", choices=("airfoil", "plasticity"))
 ap.add_argument("--sites", action="store_true")
 ap.add_argument("--only", choices=("fwd", "step"))
 ap.add_argument("--width", type=int, default=128)
@@ -41,7 +47,7 @@ args = ap.parse_args()
 
 import torch  # noqa: E402
 
-from fourierflow_amd.modules import FNOFactorized2DBlock  # noqa: E402
+from fourierflow_amd.modules import FNOFactorized2DBlock, FNOFactorizedMesh2D, FNOFactorizedMesh3D  # noqa: E402
 from fourierflow_amd.trainer import FFNOTrainer  # noqa: E402
 from oracle import ffno_oracle as orc  # noqa: E402
 
@@ -49,44 +55,72 @@ if not torch.cuda.is_available():
     raise SystemExit("time_wide.py measures on the GPU: no device found")
 dev = torch.device("cuda:0")
 PEAK_TF = 157.0
-B, G = args.batch, args.grid
+MESH = dict(airfoil=dict(size=(221, 51), batch=10, modes=(32, 16), layers=4, output_dim=1),
+            plasticity=dict(size=(101, 31, 20), batch=2, modes=(32, 12, 8), layers=4, output_dim=4))
+mesh = MESH.get(args.mesh)
 gen = torch.Generator().manual_seed(1)
-x = torch.randn(B, G, G, 3, generator=gen).to(dev)
-t = torch.randn(B, G, G, 1, generator=gen).to(dev)
+if mesh:
+    B, SIZE, nd = mesh["batch"], mesh["size"], len(mesh["size"])
+    x = torch.randn(B, *SIZE, 1, generator=gen).to(dev)      # (the model appends one coordinate channel per axis)
+    t = torch.randn(B, *SIZE, mesh["output_dim"], generator=gen).to(dev)
+    shape = dict(mesh=args.mesh, batch=B, size=list(SIZE), padding=8, layers=mesh["layers"], modes=list(mesh["modes"]), factor=4)
+else:
+    B, G = args.batch, args.grid
+    SIZE = (G, G)
+    x = torch.randn(B, G, G, 3, generator=gen).to(dev)
+    t = torch.randn(B, G, G, 1, generator=gen).to(dev)
+    shape = dict(batch=B, grid=G, layers=args.layers, modes=args.modes, factor=args.factor)
 
 
 def config(width):
+    if mesh:      # experiments/airfoil/ffno/4_layers, experiments/plasticity/ffno/4_layers
+        kw = dict(zip(("modes_x", "modes_y", "modes_z"), mesh["modes"]), width=width, input_dim=1 + nd, n_layers=mesh["layers"],
+                  share_weight=False, factor=4, ff_weight_norm=True, n_ff_layers=2, layer_norm=False)
+        return dict(kw, output_dim=mesh["output_dim"]) if nd == 3 else kw
     return dict(modes=args.modes, width=width, n_layers=args.layers, input_dim=3, share_weight=True, factor=args.factor,
                 ff_weight_norm=True, gain=0.1)
 
 
+def initial_state(width):
+    """The reference-layout state dict both sides start from (shared tensors appear under every layer's key)."""
+    if mesh:
+        torch.manual_seed(0)
+        return (FNOFactorizedMesh3D if nd == 3 else FNOFactorizedMesh2D)(**config(width)).state_dict()
+    return orc.init_block_state_dict(**config(width), seed=0)
+
+
+def oracle_model(sd, inp):
+    if mesh:
+        with torch.device(dev):      # (the oracle builds its coordinate channels on the default device, every call like the reference)
+            return (orc.ffno_mesh3d if nd == 3 else orc.ffno_mesh2d)(sd, inp, modes=mesh["modes"], n_layers=mesh["layers"])
+    return orc.ffno2d_block(sd, inp, modes=args.modes, n_layers=args.layers)["forecast"]
+
+
 def engine_sides(width):
-    """{side: callable} of our block at `width`: the inference forward and the full training step."""
+    """{side: callable} of our model at `width`: the inference forward and the full training step."""
     kw = config(width)
-    sd = orc.init_block_state_dict(**kw, seed=0)
-    blk = FNOFactorized2DBlock(**kw)
-    blk.load_state_dict(sd)
+    blk = (FNOFactorizedMesh3D if nd == 3 else FNOFactorizedMesh2D)(**kw) if mesh else FNOFactorized2DBlock(**kw)
+    blk.load_state_dict(initial_state(width))
     tr = FFNOTrainer(blk.to(dev))
     return tr, dict(fwd=lambda: tr.predict(x), step=lambda: tr.train_step(x, t))
 
 
 def oracle_sides(width):
-    kw = config(width)
     sd, uniq, seen = {}, [], {}
-    for k, v in orc.init_block_state_dict(**kw, seed=0).items():      # the shared Fourier weights appear under every layer's key
+    for k, v in initial_state(width).items():      # the shared Fourier weights appear under every layer's key
         if id(v) not in seen:
-            seen[id(v)] = v.to(dev).requires_grad_(True)
+            seen[id(v)] = v.detach().to(dev).requires_grad_(True)
             uniq.append(seen[id(v)])
         sd[k] = seen[id(v)]
     opt = torch.optim.AdamW(uniq, lr=2.5e-3, weight_decay=1e-4)
 
     def fwd():
         with torch.no_grad():
-            return orc.ffno2d_block(sd, x, modes=args.modes, n_layers=args.layers)["forecast"]
+            return oracle_model(sd, x)
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = orc.lp_rel_loss(orc.ffno2d_block(sd, x, modes=args.modes, n_layers=args.layers)["forecast"], t)
+        loss = orc.lp_rel_loss(oracle_model(sd, x), t)
         loss.backward()
         opt.step()
         return loss
@@ -152,14 +186,13 @@ if args.sites:
         tf = flops[name] / (ms * 1e-3) / 1e12 if name in flops and ms > 0 else None
         rows.append(dict(site=name, launches=n, ms=round(ms, 4), gflop=round(flops.get(name, 0) / 1e9, 3),
                          tf_per_s=None if tf is None else round(tf, 2), of_peak=None if tf is None else round(tf / PEAK_TF, 4)))
-    print(json.dumps(dict(width=args.width, shape=dict(batch=B, grid=G, layers=args.layers, modes=args.modes, factor=args.factor),
+    print(json.dumps(dict(width=args.width, shape=shape,
                           step_device_ms=round(sum(ms for _, ms in totals.values()), 4), peak_tf=PEAK_TF, sites=rows,
-                          workspace_bytes_per_layer=eng.workspace_bytes_per_layer(B, G, G))))
+                          workspace_bytes_per_layer=eng.workspace_bytes_per_layer(B, *SIZE))))
     sys.exit(0)
 
-out = dict(shape=dict(batch=B, grid=G, layers=args.layers, modes=args.modes, factor=args.factor, rounds=args.rounds,
-                      seconds=args.seconds), rows=[])
-for width in [int(w) for w in args.widths.split(",")] + [64]:
+out = dict(shape=dict(shape, rounds=args.rounds, seconds=args.seconds), rows=[])
+for width in [int(w) for w in args.widths.split(",")] + ([] if mesh else [64]):
     tr, ours = engine_sides(width)
     sides = {f"engine_{k}": v for k, v in ours.items()}
     if width != 64:
