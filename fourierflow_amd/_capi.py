@@ -9,7 +9,7 @@ import ctypes as C
 
 # generation of include/ffno.h these signatures and struct mirrors belong to (FFNO_ABI_VERSION there; _lib.check_abi compares
 # it with what the loaded library reports before anything is called)
-ABI_VERSION = 15
+ABI_VERSION = 16
 BRANCH_SELF_RANGE = 1      # ffno_fused_branch.flags: FFNO_BRANCH_SELF_RANGE (ffno_spectral_x3_mix_pair)
 
 P = C.c_void_p
@@ -158,6 +158,12 @@ class BgemmDesc(C.Structure):
     _fields_ = ([(n, P) for n in ("A", "B", "D", "bias", "gate", "resid")]
                 + [(f"{t}_{s}", C.c_int64) for t in "abd" for s in ("rs", "cs", "g0", "g1")]
                 + [(n, C.c_int32) for n in ("M", "N", "K", "G0", "G1")] + [("alpha", F), ("relu", C.c_int32), ("accumulate", C.c_int32)])
+
+
+class BgemmFfDesc(C.Structure):
+    """Mirror of ``ffno_bgemm_ff_desc`` (include/ffno.h)."""
+    _fields_ = ([(n, P) for n in ("S", "W1", "b1", "W2", "b2", "resid", "out")]
+                + [(n, C.c_int64) for n in ("P", "s_rs", "out_rs", "resid_rs")] + [("C", C.c_int32), ("H", C.c_int32)])
 
 
 GATHER_MAX_FIELDS = 8      # FFNO_GATHER_MAX_FIELDS
@@ -337,6 +343,8 @@ SIGNATURES = {
     "ffno_bgemm_colsum": (I, [P, L, L, I, P, P, I, P]),
     "ffno_bgemm_pack_fw": (I, [P, P, I, I, P]),
     "ffno_bgemm_fold_fw": (I, [P, P, I, I, I, P]),
+    "ffno_bgemm_ff_supported": (I, [P]),
+    "ffno_bgemm_ff": (I, [P, P]),
     "ffno_pad_supported": (I, [I, P, P, I]),
     "ffno_pad_embed": (I, [P, P, L, I, P, P, I, P]),
     "ffno_pad_crop": (I, [P, P, L, I, P, P, I, P]),

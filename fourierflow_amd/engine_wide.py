@@ -18,7 +18,9 @@ v_mfma_f32_32x32x2_f32), channels-last [B, S_0, .., S_{D-1}, C] end to end (SURV
     Fourier weight grad X[k]^T . dY[k], batched over k (split-K over the lines), then the fold (accumulated over layers, in a
                         fixed order, with share_weight)
     feed-forward        relu(s W1^T + b1) kept in HBM;  h W2^T + b2 + x through the residual epilogue;  backward: dh through
-                        the gate epilogue, ds, and dW1, dW2 (split-K), db1, db2 (column sum)
+                        the gate epilogue, ds, and dW1, dW2 (split-K), db1, db2 (column sum).  A pass that saves nothing may run
+                        the pair as ONE launch, ffno_bgemm_ff of csrc/bgemm_ff.hip (``fuse_ff``): the same bits, h stays on the CU
+                        and the workspace holds no [pixels, hidden] tensor
     weight norm         the ffno_weightnorm_fwd / bwd descriptors of the main engine (they take any row length)
     pad, crop           (mesh operators) ffno_pad_embed / ffno_pad_crop of csrc/meshpad.hip between the dense lift / head and the
                         layers on the padded grid, and the same pair the other way round in the backward pass
@@ -27,7 +29,8 @@ The DFT tables are built once per (L, K) on the host in float64 and rounded to f
 and c_k (c_0 = 1, c_k = 2) folded in, the imaginary DC row of the inverse zeroed (irfft ignores imag(Y[0])).  K <= L // 2: the
 Nyquist bin is never kept.
 
-Every pass is recorded once per (input shape, save) as a list of C calls over pre-built descriptors and replayed.
+Every pass is recorded once per (input shape, save, fused feed-forward) as a list of C calls over pre-built descriptors and
+replayed.
 """
 from __future__ import annotations
 
@@ -46,6 +49,14 @@ HEAD_DIM = 128
 WIDE_WIDTHS = tuple(range(96, 257, 32))
 MAX_HIDDEN = 1024
 MAX_MODES = 64
+# Whether a forward-only pass runs the fused feed-forward launch by default, per MEASURED width (profiles/wide_infer.md: true only
+# where the fused median forward time is below the pair's by more than the larger of the two spreads, in the block AND the mesh
+# presets).  A width that was not measured follows the nearest measured one.
+FUSE_FF_MEASURED = {96: True, 128: True}
+
+
+def fuse_ff_default(width: int) -> bool:
+    return FUSE_FF_MEASURED[min(FUSE_FF_MEASURED, key=lambda w: (abs(w - width), w))]
 
 
 def wide_supported(width: int) -> bool:
@@ -127,6 +138,9 @@ class WideFFNOEngine(EngineCore):
         self.pad, self.O = int(padding), int(output_dim)
         self.C, self.H, self.Cin, self.L = C, H, input_dim, n_layers
         self.share_weight, self.wnorm = bool(share_weight), bool(ff_weight_norm)
+        # forward(save_for_backward=False) records one ffno_bgemm_ff per layer in place of wide_ff1 + wide_ff2; read when a pass
+        # is recorded (a pass recorded under the other value stays what it is)
+        self.fuse_ff = fuse_ff_default(width)
 
         # parameter inventory: the registration order of FFNOEngine (engine.py), reference named_parameters() names
         self.linears: Dict[str, _Lin] = {}
@@ -257,6 +271,18 @@ class WideFFNOEngine(EngineCore):
         ds.alpha, ds.relu, ds.accumulate = 1.0, int(relu), int(acc)
         ops.append(("gemm_split" if split else "gemm", name, ds, (A, B, D, bias, gate, resid)))
 
+    @staticmethod
+    def _ff(ops, name, S, W1, b1, W2, b2, resid, out, P, C, H) -> bool:
+        """Record out = relu(S W1^T + b1) W2^T + b2 (+ resid) as one launch; False (nothing recorded) if the kernel refuses it."""
+        ds = _capi.BgemmFfDesc()
+        ds.S, ds.W1, ds.b1, ds.W2, ds.b2, ds.out = (t.data_ptr() for t in (S, W1, b1, W2, b2, out))
+        ds.resid = None if resid is None else resid.data_ptr()
+        ds.P, ds.s_rs, ds.out_rs, ds.resid_rs, ds.C, ds.H = int(P), C, C, C, C, H
+        if not (W1.is_contiguous() and W2.is_contiguous()) or not _lib.get_lib().ffno_bgemm_ff_supported(ctypes.byref(ds)):
+            return False
+        ops.append(("ff", name, ds, (S, W1, b1, W2, b2, resid, out)))
+        return True
+
     def _colsum(self, ops, ws, name, X, P, N, out):
         lib = _lib.get_lib()
         ops.append(("call", name, lib.ffno_bgemm_colsum, (_p(X), N, P, N, _p(ws.cpart), _p(out), 0), (X, out)))
@@ -270,7 +296,9 @@ class WideFFNOEngine(EngineCore):
             ws.parts.append(ws.part)
         out = []
         for o in ops:
-            if o[0] == "gemm":
+            if o[0] == "ff":
+                out.append((o[1], lib.ffno_bgemm_ff, (ctypes.byref(o[2]),), o[2:]))
+            elif o[0] == "gemm":
                 if not lib.ffno_bgemm_supported(ctypes.byref(o[2])):
                     raise ValueError(f"{o[1]}: the GEMM kernels do not take this shape")
                 out.append((o[1], lib.ffno_bgemm, (ctypes.byref(o[2]),), o[2:]))
@@ -290,7 +318,8 @@ class WideFFNOEngine(EngineCore):
 
     def _workspace(self, B, sizes, save):
         """``sizes``: the spatial extents of the DATA grid; the layers run on ``sizes + padding``."""
-        key = (B, *sizes, bool(save))
+        fused = bool(self.fuse_ff) and not save
+        key = (B, *sizes, bool(save), fused)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
@@ -304,13 +333,14 @@ class WideFFNOEngine(EngineCore):
             raise ValueError("batch too large for one launch")
         f32 = dict(dtype=torch.float32, device=self.device)
         ws = type("WS", (), {})()
-        ws.P, ws.Pd, ws.part, ws.parts, ws.shape, ws.saves = P, Pd, None, [], (B, *sizes), bool(save)
+        ws.P, ws.Pd, ws.part, ws.parts, ws.shape, ws.saves, ws.fused = P, Pd, None, [], (B, *sizes), bool(save), fused
         nslot = L if save else 1
         lines = [P // S[d] for d in self.axis_of_weight]                     # per Fourier weight
         ws.x = torch.empty(Pd, Cin, **f32)
         ws.X = [torch.empty(P, C, **f32) for _ in range(2)]                  # layer inputs, ping-pong
         ws.S = [torch.empty(P, C, **f32) for _ in range(nslot)]              # spectral output = feed-forward input
-        ws.Hh = [torch.empty(P, H, **f32) for _ in range(nslot)]             # hidden activations (their sign = the ReLU gate)
+        # hidden activations (their sign = the ReLU gate); none where the pass keeps h on the CU (the fused feed-forward launch)
+        ws.Hh = [] if fused else [torch.empty(P, H, **f32) for _ in range(nslot)]
         # forward spectra [line][k][re / im][C], per Fourier weight and slot
         ws.SP = [[torch.empty(R, 2 * K * C, **f32) for _ in range(nslot)] for R, K in zip(lines, self.Ks)]
         ws.SM = torch.empty(max(R * 2 * K for R, K in zip(lines, self.Ks)) * C, **f32)      # mixed spectrum / adjoint spectrum
@@ -380,7 +410,7 @@ class WideFFNOEngine(EngineCore):
             self._pad_op(ops, ws, "wide_pad_embed", False, ws.Dn, ws.X[0])
         for l in range(L):
             sl = ws.slot(l)
-            X, Xn, S, Hh = ws.X[l % 2], ws.X[(l + 1) % 2], ws.S[sl], ws.Hh[sl]
+            X, Xn, S = ws.X[l % 2], ws.X[(l + 1) % 2], ws.S[sl]
             packs = self.packs[self._fw_set_of[l]]
             for i, (w, K, Ln, R, G0, G1, (rs, s0, s1)) in enumerate(axes):      # the layer's spectral output: the sum of the branches
                 F, Fi = self._table(Ln, K)
@@ -392,10 +422,17 @@ class WideFFNOEngine(EngineCore):
                   acc=int(i > 0))
             pfx = self.ff_prefix[l]
             l0, l1 = pfx + "layers.0.0.", pfx + "layers.1.0."
+            # the head reads the last BACKCAST, not x + b (grid_2d.py:175)
+            if ws.fused and self._ff(ops, "wide_ff", S, lin[l0].weff, bias(l0), lin[l1].weff, bias(l1), X if l < L - 1 else None,
+                                     Xn if l < L - 1 else ws.Bout, P, C, H):
+                continue
+            if not ws.Hh:     # (the fused launch refused this layer: the pair, on one hidden image)
+                ws.Hh = [torch.empty(P, H, dtype=torch.float32, device=self.device)]
+            Hh = ws.Hh[sl]
             g(ops, "wide_ff1", S, lin[l0].weff, Hh, P, H, C, (C, 1), (1, C), (H, 1), bias=bias(l0), relu=1)
             if l < L - 1:
                 g(ops, "wide_ff2", Hh, lin[l1].weff, Xn, P, C, H, (H, 1), (1, H), (C, 1), bias=bias(l1), resid=X)
-            else:     # the head reads the last BACKCAST, not x + b (grid_2d.py:175)
+            else:
                 g(ops, "wide_ff2", Hh, lin[l1].weff, ws.Bout, P, C, H, (H, 1), (1, H), (C, 1), bias=bias(l1))
         if self.pad:      # the head runs on the data grid (mesh_2d.py:158-161, mesh_3d.py:173-176)
             self._pad_op(ops, ws, "wide_pad_crop", True, ws.Bout, ws.Bd)
@@ -517,6 +554,21 @@ class WideFFNOEngine(EngineCore):
         S = self._padded(sizes)
         P = B * _prod(S)
         return 4 * (P * (self.C + self.H) + 2 * self.C * sum(P // S[d] * K for K, d in zip(self.Ks, self.axis_of_weight)))
+
+    def forward_workspace_bytes(self, B: int, *sizes: int, fused=None) -> int:
+        """The bytes of every tensor a forward-only pass (``forward(save_for_backward=False)``) keeps for a batch of ``B`` on a
+        ``sizes`` data grid, without allocating them; ``fused``: with the fused feed-forward launch (default: ``fuse_ff``), which
+        needs no [pixels, hidden] image -- exactly 4 P H bytes less, P the pixels of the padded grid."""
+        fused = bool(self.fuse_ff) if fused is None else bool(fused)
+        S = self._padded(sizes)
+        C, H = self.C, self.H
+        P, Pd = B * _prod(S), B * _prod(sizes)
+        lines = [(P // S[d], K) for K, d in zip(self.Ks, self.axis_of_weight)]
+        n = Pd * self.Cin + 4 * P * C + (0 if fused else P * H)                      # x; X (two), S, Bout; Hh
+        n += sum(R * 2 * K * C for R, K in lines) + 2 * max(R * 2 * K for R, K in lines) * C      # SP; SM, SD
+        n += (2 * Pd * C if self.pad else 0) + Pd * (HEAD_DIM + self.O)              # Dn, Bd; T0, y
+        n += int(_lib.get_lib().ffno_bgemm_colsum_ws_floats(P, max(H, HEAD_DIM, C))) + 1      # cpart; part
+        return 4 * n
 
 
 class WideFFNO2DEngine(WideFFNOEngine):

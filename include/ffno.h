@@ -82,8 +82,9 @@ const char* ffno_build_target(void);
  * does: fourierflow_amd/_lib.py refuses a mismatch).  9: ffno_vorticity_coarsen_* / ffno_markov_corr_metrics, which the host
  * binds at load -- a library of generation 8 lacks them.  10: ffno_prediction_export_step / ffno_energy_spectrum, bound at load
  * in the same way.  12: ffno_ns2d_cn_update_harmonic / ffno_ns2d_harmonic_force, likewise.  13: ffno_nudft_axis_* /
- * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise.  14: ffno_bgemm*, likewise.  15: ffno_pad_*, likewise. */
-#define FFNO_ABI_VERSION 15
+ * ffno_axis_modes_to_grid / ffno_grid_to_axis_modes, likewise.  14: ffno_bgemm*, likewise.  15: ffno_pad_*, likewise.  16: ffno_bgemm_ff*,
+ * likewise. */
+#define FFNO_ABI_VERSION 16
 int ffno_abi_version(void);
 
 /* word[0] = max(word[0], bits(max |x[i]|)): folds a tensor into a range word (see "Range words" above) */
@@ -1380,6 +1381,35 @@ size_t ffno_bgemm_colsum_ws_floats(long P, int N);
 int ffno_bgemm_colsum(const float* X, long row_stride, long P, int N, float* partial, float* out, int accumulate, void* stream);
 int ffno_bgemm_pack_fw(const float* w, float* Wb, int C, int K, void* stream);
 int ffno_bgemm_fold_fw(const float* G, float* dw, int C, int K, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Fused feed-forward of the wide block for a pass that saves nothing (csrc/bgemm_ff.hip): FeedForward (feedforward.py:13-19) and
+ * the block's residual (grid_2d.py:169) in ONE launch,
+ *     out[p][c] = ( sum_j relu( sum_i S[p][i] W1[j][i] + b1[j] ) W2[c][j] ) + b2[c]  (+ resid[p][c])
+ * in place of ffno_bgemm (relu, bias) writing h [P][H] to HBM and ffno_bgemm (bias, resid) reading it back.  The hidden image stays
+ * on the CU.  Same instruction and summation order as the pair (each hidden unit one accumulator over i in ascending pairs, + b1,
+ * max(., 0); each output one accumulator over j in ascending pairs, + b2, + resid): the result is the pair's bit for bit.
+ *   S, out, resid: [P][C] with unit column stride and row strides s_rs, out_rs, resid_rs (floats); resid may be NULL (the last
+ *   layer writes the bare backcast).  W1 [H][C] and W2 [C][H] dense row-major; b1 [H], b2 [C].
+ *   Supported: C a multiple of 32 in 96 .. 256; H a multiple of 32 in 32 .. 1024; P >= 1; row strides >= C and multiples of 4;
+ *   S, W1, W2, out, resid 16-byte aligned; out overlaps neither S nor resid.
+ *   FFNO_EINVAL: NULL desc / S / W1 / b1 / W2 / b2 / out, P < 1.  FFNO_EUNSUPPORTED: everything else outside the list above.  Nothing
+ *   is launched then.  ffno_bgemm_ff_supported: 1 iff ffno_bgemm_ff would take the descriptor.
+ * No workspace, no atomics (two calls give the same bits); the call only enqueues on `stream`.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct ffno_bgemm_ff_desc {
+    const float* S;
+    const float* W1;
+    const float* b1;
+    const float* W2;
+    const float* b2;
+    const float* resid; /* or NULL */
+    float* out;
+    int64_t P, s_rs, out_rs, resid_rs;
+    int32_t C, H;
+} ffno_bgemm_ff_desc;
+int ffno_bgemm_ff_supported(const ffno_bgemm_ff_desc* desc);
+int ffno_bgemm_ff(const ffno_bgemm_ff_desc* desc, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Zero padding and cropping of channels-last fp32 activations: the WIDE mesh operators (FNOFactorizedMesh2D / Mesh3D at widths

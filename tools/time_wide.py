@@ -16,9 +16,16 @@ rounds and their spread.  One JSON line; profiles/wide_engine.md holds a run.  F
                          at the reference configs' other hyper-parameters, against oracle.ffno_oracle.ffno_mesh2d / ffno_mesh3d;
                          no width-64 row.  profiles/wide_mesh.md holds a run.  Goes with --sites and --only as well.
   --sites --width W      per call site of one wide training step: launches, shape-derived FLOPs, device time (HIP events
-                         around every launch) and the achieved TF/s against the 157 TF fp32 matrix peak
-  --only fwd|step --width W [--iters I]   that side alone after a warm-up: what a `rocprofv3 --kernel-trace --stats` run of its
-                                          own is pointed at
+                         around every launch) and the achieved TF/s against the 157 TF fp32 matrix peak; the same for one
+                         forward-only pass with the fused feed-forward launch (`infer_sites`: wide_ff in place of wide_ff1 +
+                         wide_ff2) and without it (`infer_pair_sites`)
+  --only fwd|step --width W [--iters I] [--fuse-ff 0|1]   that side alone after a warm-up: what a `rocprofv3 --kernel-trace
+                         --stats` run of its own is pointed at; --fuse-ff sets the engine's fuse_ff for the forward
+  --infer                the forward-only pass with the fused feed-forward launch (csrc/bgemm_ff.hip, engine.fuse_ff = True) against
+                         the same pass on the pair of launches (fuse_ff = False): ONE engine instance and one set of weights, the
+                         two recorded passes alternating in this process, --rounds rounds, median and spread = max - min; also
+                         whether the two outputs are equal bit for bit, and the workspace of each.  With --widths, and with --mesh.
+                         profiles/wide_infer.md holds a run.
 """
 import argparse
 import json
@@ -43,6 +50,8 @@ ap.add_argument("--sites", action="store_true")
 ap.add_argument("--only", choices=("fwd", "step"))
 ap.add_argument("--width", type=int, default=128)
 ap.add_argument("--iters", type=int, default=3)
+ap.add_argument("--infer", action="store_true")
+ap.add_argument("--fuse-ff", type=int, choices=(0, 1))
 args = ap.parse_args()
 
 import torch  # noqa: E402
@@ -161,8 +170,51 @@ class SiteTimer:
         return {n: (len(ev), sum(a.elapsed_time(b) for a, b in ev)) for n, ev in self.events.items()}
 
 
+def set_fuse(eng, on):
+    def run():
+        eng.fuse_ff = on
+        return tr.predict(x)
+    return run
+
+
+if args.infer:
+    out = dict(shape=dict(shape, rounds=args.rounds, seconds=args.seconds), rows=[])
+    for width in [int(w) for w in args.widths.split(",")]:
+        tr, _ = engine_sides(width)
+        eng = tr.engine
+        sides = dict(fused=set_fuse(eng, True), pair=set_fuse(eng, False))
+        y, recorded = {}, {}
+        for name, fn in sides.items():
+            y[name] = fn().clone()
+            recorded[name] = sorted({o[0] for o in eng._last.fwd if o[0].startswith("wide_ff")})
+        iters = {}
+        for name, fn in sides.items():
+            timed(fn, 2)
+            iters[name] = max(1, int(args.seconds * 1e3 / args.rounds / timed(fn, 2)) + 1)
+        rounds = {name: [] for name in sides}
+        for _ in range(args.rounds):
+            for name, fn in sides.items():
+                rounds[name].append(timed(fn, iters[name]))
+        row = dict(width=width, bit_identical=bool(torch.equal(y["fused"], y["pair"])), feed_forward_sites=recorded)
+        for name, r in rounds.items():
+            row[name] = dict(ms=round(statistics.median(r), 4), spread_ms=round(max(r) - min(r), 4), iters_per_round=iters[name],
+                             rounds=[round(v, 4) for v in r],
+                             workspace_bytes=eng.forward_workspace_bytes(B, *SIZE, fused=name == "fused"))
+        gain = row["pair"]["ms"] - row["fused"]["ms"]
+        row["pair_minus_fused_ms"] = round(gain, 4)
+        row["pair_over_fused"] = round(row["pair"]["ms"] / row["fused"]["ms"], 4)
+        # the rule of profiles/wide_infer.md: the fused median below the pair's by more than the larger of the two spreads
+        row["fused_wins"] = bool(gain > max(row["fused"]["spread_ms"], row["pair"]["spread_ms"]))
+        out["rows"].append(row)
+        del tr, eng, sides
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+    sys.exit(0)
+
 if args.only:
     tr, sides = engine_sides(args.width)
+    if args.fuse_ff is not None:
+        tr.engine.fuse_ff = bool(args.fuse_ff)
     timed(sides[args.only], 2)
     print(json.dumps(dict(side=args.only, width=args.width, iters=args.iters, ms=round(timed(sides[args.only], args.iters), 4))))
     sys.exit(0)
@@ -181,14 +233,37 @@ if args.sites:
         d = keep[0] if keep and hasattr(keep[0], "G0") else None
         if d is not None:
             flops[name] = flops.get(name, 0) + 2.0 * d.M * d.N * d.K * d.G0 * d.G1
-    rows = []
-    for name, (n, ms) in sorted(totals.items(), key=lambda kv: -kv[1][1]):
-        tf = flops[name] / (ms * 1e-3) / 1e12 if name in flops and ms > 0 else None
-        rows.append(dict(site=name, launches=n, ms=round(ms, 4), gflop=round(flops.get(name, 0) / 1e9, 3),
-                         tf_per_s=None if tf is None else round(tf, 2), of_peak=None if tf is None else round(tf / PEAK_TF, 4)))
+    def site_rows(totals, flops):
+        rows = []
+        for name, (n, ms) in sorted(totals.items(), key=lambda kv: -kv[1][1]):
+            tf = flops[name] / (ms * 1e-3) / 1e12 if name in flops and ms > 0 else None
+            rows.append(dict(site=name, launches=n, ms=round(ms, 4), gflop=round(flops.get(name, 0) / 1e9, 3),
+                             tf_per_s=None if tf is None else round(tf, 2), of_peak=None if tf is None else round(tf / PEAK_TF, 4)))
+        return rows
+
+    def infer_sites(fuse):
+        """One forward-only pass, with or without the fused feed-forward launch."""
+        run = set_fuse(eng, fuse)
+        timed(run, 2)
+        t = eng.timer = SiteTimer()
+        run()
+        eng.timer = None
+        fl = {}
+        for name, _fn, _args, keep in eng._last.fwd:
+            d = keep[0] if keep else None
+            if hasattr(d, "G0"):
+                fl[name] = fl.get(name, 0) + 2.0 * d.M * d.N * d.K * d.G0 * d.G1
+            elif hasattr(d, "W1"):      # the fused feed-forward descriptor: both products
+                fl[name] = fl.get(name, 0) + 4.0 * d.P * d.C * d.H
+        return site_rows(t.totals(), fl)
+
+    rows = site_rows(totals, flops)
     print(json.dumps(dict(width=args.width, shape=shape,
                           step_device_ms=round(sum(ms for _, ms in totals.values()), 4), peak_tf=PEAK_TF, sites=rows,
-                          workspace_bytes_per_layer=eng.workspace_bytes_per_layer(B, *SIZE))))
+                          infer_sites=infer_sites(True), infer_pair_sites=infer_sites(False),
+                          workspace_bytes_per_layer=eng.workspace_bytes_per_layer(B, *SIZE),
+                          forward_workspace_bytes=dict(fused=eng.forward_workspace_bytes(B, *SIZE, fused=True),
+                                                       pair=eng.forward_workspace_bytes(B, *SIZE, fused=False)))))
     sys.exit(0)
 
 out = dict(shape=dict(shape, rounds=args.rounds, seconds=args.seconds), rows=[])
